@@ -7,9 +7,12 @@
 One *step* (scope A) = [per-batch edge bookkeeping -> extractor MLP fwd -> concrete sample ->
 symmetrise | lift -> L masked aggregations fwd] + the backward of all of it (+ the flat RCCL gradient all-reduce
 when N > 1), on one synthetic collated batch resident in HBM.  `value` = directed edges of all ranks / step time.
-The full GSAT training step (both backbone passes, dense node updates, losses, Adam) is timed next to it and
-reported as `full_step`; the CPU oracle timed on the host cores is `cpu_baseline`; `roofline` prices the masked
-aggregation forward kernel against HBM bandwidth.
+A plain run times that step and nothing else.  With `--full` it also re-times the step on exact fp32 products
+(`value_fp32_exact`), times the full GSAT training step (both backbone passes, dense node updates, losses, Adam) as
+`full_step`, times the CPU oracle on the host cores as `cpu_baseline`, and prices the masked aggregation kernels
+against HBM bandwidth as `roofline`; without `--full` those fields are null.
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
 """
 from __future__ import annotations
 
@@ -98,10 +101,24 @@ class HotPath:
         self.gouts = [torch.randn(N, width, generator=g).to(dev) for _ in range(L)]
         self.flat = None
         self.reuse_index = False
+        self.keep_outputs = False      # --dump-outputs: hold the forward results of the latest step (in a captured step: the graph's buffers)
+        self.last = None
 
     def attach_dp(self):
         from dp_gsat_amd.dist import FlatGradAllReduce
         self.flat = FlatGradAllReduce(self.ext.parameters())
+
+    def outputs(self):
+        """What a caller of the step receives, by name: the forward results of the latest step and the gradients its backward left."""
+        out = dict(self.last)
+        out["grad_emb"] = self.emb.grad
+        for l, t in enumerate(self.xs):
+            out[f"grad_x_l{l}"] = t.grad
+        for l, t in enumerate(self.edge_emb or []):
+            out[f"grad_edge_emb_l{l}"] = t.grad
+        for n, p in self.ext.named_parameters():
+            out["grad_ext." + n] = p.grad
+        return {k: v for k, v in out.items() if v is not None}
 
     def step(self):
         self.compute()
@@ -129,7 +146,7 @@ class HotPath:
             t.grad = None
         index = G.get_index(d.edge_index, self.N)
         index.graphs(d.batch, d.num_graphs)
-        _, att = self.ext.attend(self.emb, d.edge_index, d.batch, noise="philox")      # concrete-sample noise drawn in the head kernel
+        logits, att = self.ext.attend(self.emb, d.edge_index, d.batch, noise="philox")      # concrete-sample noise drawn in the head kernel
         edge_att = G.symmetrise_edge_att(att, d.edge_index, self.N) if wl["edge_att"] else G.lift_node_att_to_edge_att(att, d.edge_index)
         outs = []
         for l in range(wl["L"]):
@@ -138,6 +155,10 @@ class HotPath:
             else:
                 outs.append(G.ops.masked_sum_aggregate(self.xs[l], index, edge_att, self.edge_emb[l] if self.gine else None))
         torch.autograd.backward(outs, self.gouts)
+        if self.keep_outputs:
+            self.last = dict(att_log_logits=logits.detach(), att=att.detach(), **{f"out_l{l}": o.detach() for l, o in enumerate(outs)})
+            if isinstance(edge_att, torch.Tensor):      # node attention stays a lazy view (LiftedAttention) of `att`: nothing more to keep
+                self.last["edge_att"] = edge_att.detach()
 
 
 class FullStep:
@@ -205,6 +226,34 @@ def timed(step_fn, steps, warmup, dev, distributed):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_BYTES = 60_000_000       # array bytes --dump-outputs writes in all (with their .npy headers the files stay below 64 MB)
+DUMP_WHOLE_BYTES = 1 << 20    # an array of at most this many bytes is always written whole
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BYTES):
+    """--dump-outputs: every array as <out_dir>/<name>.npy, in float32 (float64 stays float64).  When they hold more than `budget`
+    bytes in all, each array larger than DUMP_WHOLE_BYTES keeps the same fraction of its rows, chosen so that the total fits: a
+    sorted sample drawn by a generator seeded with 0, so the same shape keeps the same rows in every run and every build.
+    Returns each array's full shape and how many of its rows were written (null: all of them), for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach() if v.dtype == torch.float64 else v.detach().float() for k, v in arrays.items()}
+    nbytes = {k: v.numel() * v.element_size() for k, v in arrays.items()}
+    sampled = {k for k, v in arrays.items() if nbytes[k] > DUMP_WHOLE_BYTES and v.dim() >= 1 and v.shape[0] > 1}
+    frac = 1.0
+    if sum(nbytes.values()) > budget:
+        frac = max(budget - sum(n for k, n in nbytes.items() if k not in sampled), 0) / sum(nbytes[k] for k in sampled)
+    manifest = {}
+    for name, t in arrays.items():
+        shape, kept = list(t.shape), None
+        if name in sampled and frac < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], max(1, int(t.shape[0] * frac)), replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+            kept = len(rows)
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+        manifest[name] = dict(shape=shape, rows_kept=kept)
+    return manifest
 
 
 # ------------------------------------------------------------------------------------------------
@@ -475,10 +524,15 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--reuse-index", action="store_true", help="keep the per-batch bookkeeping cached across steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-step", action="store_true")
-    ap.add_argument("--no-exact-rerun", action="store_true", help="skip the second timing with the extractor's backward products on exact fp32")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the roofline leg (profiles of the timed region without its extra launches)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the exact-fp32 re-timing, the whole training step, "
+                                                         "the roofline leg and the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all: larger outputs "
+                         "as a fixed, seeded sample of their rows; the result line's `dump_outputs` gives the full shapes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-full-step", action="store_true", help="with --full: skip the whole training step")
+    ap.add_argument("--no-exact-rerun", action="store_true", help="with --full: skip the second timing with the extractor's backward products on exact fp32")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     ap.add_argument("--cpu-sample-graphs", type=int, default=0)
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="capture the step into a hipGraph (torch.cuda.graph) and time replays; DEFAULT on one GPU for c1-c4: the fork's "
@@ -539,6 +593,7 @@ def main():
         return
     hot = HotPath(wl, data, dev, seed=args.seed + rank)
     hot.reuse_index = args.reuse_index
+    hot.keep_outputs = bool(args.dump_outputs) and rank == 0
     if distributed:
         hot.attach_dp()
     def captured(fn):
@@ -571,6 +626,9 @@ def main():
     else:
         step_fn = captured(hot.step) if args.graph else hot.step
     dt = timed(step_fn, args.steps, args.warmup, dev, distributed)
+    dumped = None
+    if hot.keep_outputs:
+        dumped = dump_outputs(hot.outputs(), args.dump_outputs)      # before any --full leg runs the step again
     e_local = torch.tensor([float(data.num_edges), float(data.num_nodes)], dtype=torch.float64, device=dev)
     if distributed:
         dist.all_reduce(e_local)
@@ -587,7 +645,7 @@ def main():
     # the same step with every extractor product on exact fp32 MFMA (GSAT_ATTN_BWD_SPLIT=0, staged forward), measured in the same
     # process so that the line says what the default costs / buys
     value_exact = ms_exact = None
-    if world == 1 and not distributed and not args.no_exact_rerun:
+    if args.full and world == 1 and not distributed and not args.no_exact_rerun:
         os.environ["GSAT_ATTN_BWD_SPLIT"] = "0"
         fused_env = os.environ.get("GSAT_ATTN_FUSED")
         os.environ["GSAT_ATTN_FUSED"] = "0"            # the staged forward: exact fp32 MFMA
@@ -604,7 +662,7 @@ def main():
                 os.environ["GSAT_ATTN_FUSED"] = fused_env
 
     full = None
-    if not args.no_full_step:
+    if args.full and not args.no_full_step:
         # the whole training step of C3 is GPU-bound by a wide margin (4.6 ms) and measures ~4 % better eager than captured (capturable
         # Adam, device-side seeds): unless a mode was asked for, only the launch-bound workloads replay it as a graph
         full_graph = bool(args.graph) and (mode_given or args.workload != "c3") and not distributed      # N > 1: forward/backward, all-reduce, Adam stay eager
@@ -635,7 +693,7 @@ def main():
 
     G.set_sync_free(False)
     roof, cpu = None, None
-    if rank == 0:
+    if args.full and rank == 0:
         hot.reuse_index = True
         hot.flat = None          # rank 0 alone runs this leg: its in-step timing must not enter the gradient all-reduce (the other ranks wait at the barrier below)
         roof = None if args.no_roofline else aggregation_roofline(wl, data, dev, step_fn=hot.step)
@@ -659,6 +717,8 @@ def main():
                        "parallelism": f"dp{world}", "index_rebuilt_every_step": not args.reuse_index, "hipgraph": bool(args.graph), "sync_free": bool(args.graph or args.sync_free)},
             "roofline": roof, "cpu_baseline": cpu, "full_step": full,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dict(dir=args.dump_outputs, arrays=dumped)
         if cpu:
             line["speedup_vs_cpu_port"] = round(value / world / cpu["value"], 1) if cpu["value"] > 0 else None
         print(json.dumps(line))

@@ -177,7 +177,7 @@ def test_bench_runs_with_two_ranks(dev, mode):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c1", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--backend", "gloo", mode]
+           "--full", "--no-cpu-baseline", "--backend", "gloo", mode]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -28,20 +28,37 @@ def build_oracle(case, backbone, learn_edge_att, H=16):
     return cfg, clf, ext
 
 
+def run_oracle(c, backbone, edge, dtype):
+    """forward_pass + backward of the oracle on a golden case, in `dtype`: named outputs (loss included) and the extractor's gradients."""
+    _, clf, ext = build_oracle(c, backbone, edge)
+    clf, ext = clf.to(dtype), ext.to(dtype)
+    gsat = om.GSAT(clf, ext, om.Criterion(2, False), learn_edge_att=edge).train()
+    data = NS(x=c["x"].to(dtype), edge_index=c["edge_index"], batch=c["batch"], edge_attr=None, y=c["y"].to(dtype))
+    edge_att, loss, ld, logits, aux = gsat.forward_pass(data, 12, True, u=c["u"].to(dtype), masks=[c["mask1"].to(dtype), c["mask2"].to(dtype)])
+    loss.backward()
+    outs = dict(emb=aux["emb"], att_log_logits=aux["att_log_logits"], att=aux["att"], edge_att=edge_att, clf_logits=logits, loss=loss.view(1))
+    return outs, {k: p.grad for k, p in ext.named_parameters()}
+
+
+def assert_golden(v, v64, ref, atol, rtol, what):
+    """|v - ref| <= atol + rtol * |ref|, plus 4 x the fp32 oracle's own rounding error on this host (max |v - v64|, the slack of
+    tests/util.close): the fixture holds one host's fp32 summation order, and PNA's std aggregator turns another host's order
+    into ~1e-5 of emb.  A change of the oracle's formulas moves v and v64 together, so it is not covered by the slack."""
+    v, v64, ref = v.detach().double(), v64.detach().double(), ref.double().view(v.shape)
+    slack = 4.0 * (v - v64).abs().max().item()
+    assert ((v - ref).abs() <= atol + rtol * ref.abs() + slack).all(), what
+
+
 @pytest.mark.parametrize("name,backbone,edge", [("gin_edge", "GIN", True), ("pna_node", "PNA", False)])
 def test_oracle_reproduces_golden(name, backbone, edge):
     c = load_case(name)
-    _, clf, ext = build_oracle(c, backbone, edge)
-    gsat = om.GSAT(clf, ext, om.Criterion(2, False), learn_edge_att=edge).train()
-    data = NS(x=c["x"], edge_index=c["edge_index"], batch=c["batch"], edge_attr=None, y=c["y"])
-    edge_att, loss, ld, logits, aux = gsat.forward_pass(data, 12, True, u=c["u"], masks=[c["mask1"], c["mask2"]])
-    loss.backward()
-    for k, v in (("emb", aux["emb"]), ("att_log_logits", aux["att_log_logits"]), ("att", aux["att"]),
-                 ("edge_att", edge_att), ("clf_logits", logits)):
-        assert torch.allclose(v, c[k], atol=1e-6, rtol=1e-5), k
-    assert abs(loss.item() - c["loss"].item()) < 1e-6
-    for k, p in ext.named_parameters():
-        assert torch.allclose(p.grad, c["grad.ext." + k], atol=1e-6, rtol=1e-4), k
+    outs, grads = run_oracle(c, backbone, edge, torch.float32)
+    outs64, grads64 = run_oracle(c, backbone, edge, torch.float64)
+    for k in ("emb", "att_log_logits", "att", "edge_att", "clf_logits"):
+        assert_golden(outs[k], outs64[k], c[k], 1e-6, 1e-5, k)
+    assert_golden(outs["loss"], outs64["loss"], c["loss"], 1e-6, 0.0, "loss")
+    for k, g in grads.items():
+        assert_golden(g, grads64[k], c["grad.ext." + k], 1e-6, 1e-4, k)
 
 
 def test_mutag_fixture_matches_reference_facts():

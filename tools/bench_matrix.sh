@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 for wl in c3 c1 c2 c4; do
   for mode in "--eager" "--graph"; do
-    python bench.py --workload $wl $mode --no-cpu-baseline 2>gpurun_out/matrix_$wl$mode.err | tail -1 | python -c "
+    python bench.py --workload $wl $mode --full --no-cpu-baseline | tail -1 | python -c "
 import sys, json
 r = json.loads(sys.stdin.read())
 f = r.get('full_step') or {}
