@@ -496,25 +496,38 @@ def new_seed() -> int:
     return int(torch.empty((), dtype=torch.int64).random_().item())
 
 
+# device -> [state int64[2] = (base, counter), the torch.initial_seed() the base was drawn under].  A state tensor lives as long as the
+# process: every captured graph that drew a seed holds its address in a gsat_seed_next node, so it is re-based in place, never freed.
 _DEVICE_SEEDS = {}
 
 
 def device_seed(device) -> torch.Tensor:
     """A fresh 1-element int64 seed tensor on ``device`` for a captured (sync-free) step: the next value of a device-resident counter stream
-    (gsat_seed_next: one launch; torch's graph-safe ``random_()`` takes three).  The stream's base comes from torch's CPU generator the first
-    time a (device, torch.initial_seed()) pair is seen, so ``torch.manual_seed`` restarts it; it must first be used outside a capture
-    (warm-up runs do), otherwise this falls back to ``random_()``."""
-    key = (str(device), torch.initial_seed())
-    st = _DEVICE_SEEDS.get(key)
-    if st is None:
-        if torch.cuda.is_current_stream_capturing() or os.environ.get("GSAT_DEVICE_SEEDS", "1") == "0":
+    (gsat_seed_next: one launch; torch's graph-safe ``random_()`` takes three).  The stream's base comes from torch's CPU generator.  When
+    ``torch.initial_seed()`` has changed since (``torch.manual_seed``), the next call outside a capture re-bases the stream in place (new
+    base, counter 0), so graphs captured earlier follow the new seed too.  The first call must come outside a capture (warm-up runs do),
+    otherwise this falls back to ``random_()``, as it always does with GSAT_DEVICE_SEEDS=0."""
+    if os.environ.get("GSAT_DEVICE_SEEDS", "1") == "0":
+        return torch.empty(1, dtype=torch.int64, device=device).random_()
+    capturing = torch.cuda.is_current_stream_capturing()
+    ent = _DEVICE_SEEDS.get(str(device))
+    if ent is None:
+        if capturing:
             return torch.empty(1, dtype=torch.int64, device=device).random_()
-        st = torch.tensor([new_seed(), 0], dtype=torch.int64, device=device)
-        _DEVICE_SEEDS.clear()
-        _DEVICE_SEEDS[key] = st
+        ent = [torch.tensor([new_seed(), 0], dtype=torch.int64, device=device), torch.initial_seed()]
+        _DEVICE_SEEDS[str(device)] = ent
+    elif ent[1] != torch.initial_seed() and not capturing:
+        ent[0].copy_(torch.tensor([new_seed(), 0], dtype=torch.int64))
+        ent[1] = torch.initial_seed()
     out = torch.empty(1, dtype=torch.int64, device=device)
-    call("gsat_seed_next", ptr(st), ptr(out), stream())
+    call("gsat_seed_next", ptr(ent[0]), ptr(out), stream())
     return out
+
+
+def device_seed_state(device) -> Optional[torch.Tensor]:
+    """The (base, counter) int64[2] state behind ``device_seed`` on ``device`` (None before its first use): for tests and diagnostics."""
+    ent = _DEVICE_SEEDS.get(str(device))
+    return None if ent is None else ent[0]
 
 
 class Sample(torch.autograd.Function):

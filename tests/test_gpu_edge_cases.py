@@ -5,7 +5,7 @@ import torch
 
 from oracle import bookkeeping as obk
 from oracle import modules as om
-from oracle import ops as oops
+from tests.replay import scope_a_reference
 from tests.util import close
 
 pytestmark = pytest.mark.gpu
@@ -150,47 +150,32 @@ def test_scope_a_at_baseline_size(dev, workload):
     u = torch.rand(M, 1, generator=g).clamp_(1e-10, 1 - 1e-10)
     masks = [(torch.rand(M, C1, generator=g) > 0.5).float(), (torch.rand(M, H, generator=g) > 0.5).float()]
     oext = om.ExtractorMLP(H, edge).train()
-
-    def run_oracle(dt):
-        ext = om.ExtractorMLP(H, edge).to(dt).train()
-        ext.load_state_dict({k: v.to(dt) for k, v in oext.state_dict().items()})
-        e = emb.to(dt).clone().requires_grad_(True)
-        xl = [t.to(dt).clone().requires_grad_(True) for t in xs]
-        att = oops.concrete_sample(ext(e, data.edge_index, data.batch, masks=[m.to(dt) for m in masks]), u.to(dt), True)
-        if edge:
-            rev = torch.from_numpy(obk.reverse_edge_perm(data.edge_index, N)) if obk.is_undirected(data.edge_index, N) else None
-            ea = oops.symmetrise(att, rev)
-        else:
-            ea = oops.lift_node_att_to_edge_att(att, data.edge_index)
-        outs = []
-        for l in range(L):
-            if wl["backbone"] == "PNA":
-                outs.append(oops.pna_aggregate(xl[l], data.edge_index, ea, bench.PNA_AGGR, ["identity"], {"lin": 1.0, "log": 1.0}))
-            elif gine:
-                outs.append(oops.gine_aggregate(xl[l], data.edge_index, ees[l].to(dt), ea))
-            else:
-                outs.append(oops.gin_aggregate(xl[l], data.edge_index, ea))
-        torch.autograd.backward(outs, [t.to(dt) for t in gouts])
-        return dict(att=att, ea=ea, out0=outs[0], demb=e.grad, dx0=xl[0].grad, dW1=ext.feature_extractor[0].weight.grad,
-                    dW3=ext.feature_extractor[8].weight.grad)
-
-    r32, r64 = run_oracle(torch.float32), run_oracle(torch.float64)
+    r32, r64 = (scope_a_reference(wl, data, emb, xs, ees, gouts, u, masks, oext.state_dict(), dt) for dt in (torch.float32, torch.float64))
     d = data.to(dev)
     ext = G.ExtractorMLP(H, edge).to(dev).train()
     ext.load_state_dict(oext.state_dict())
     e = emb.to(dev).requires_grad_(True)
     xl = [t.to(dev).requires_grad_(True) for t in xs]
+    eel = [t.to(dev).requires_grad_(True) for t in ees] if gine else None
     index = G.get_index(d.edge_index, N)
-    _, att = ext.attend(e, d.edge_index, d.batch, noise=u.to(dev), dropout_masks=[m.to(dev) for m in masks])
+    logits, att = ext.attend(e, d.edge_index, d.batch, noise=u.to(dev), dropout_masks=[m.to(dev) for m in masks])
     ea = G.symmetrise_edge_att(att, d.edge_index, N) if edge else G.lift_node_att_to_edge_att(att, d.edge_index)
     outs = []
     for l in range(L):
         if wl["backbone"] == "PNA":
             outs.append(G.ops.pna_aggregate(xl[l], index, ea, None, bench.PNA_AGGR, ["identity"], {"lin": 1.0, "log": 1.0}))
         else:
-            outs.append(G.ops.masked_sum_aggregate(xl[l], index, ea, ees[l].to(dev) if gine else None))
+            outs.append(G.ops.masked_sum_aggregate(xl[l], index, ea, eel[l] if gine else None))
     torch.autograd.backward(outs, [t.to(dev) for t in gouts])
-    got = dict(att=att, ea=ea, out0=outs[0], demb=e.grad, dx0=xl[0].grad, dW1=ext.mlp.linears()[0].weight.grad, dW3=ext.mlp.linears()[2].weight.grad)
+    # every output of the step, by the names bench.HotPath.outputs() uses
+    got = dict(att_log_logits=logits, att=att, edge_att=ea, grad_emb=e.grad)
+    for l in range(L):
+        got[f"out_l{l}"], got[f"grad_x_l{l}"] = outs[l], xl[l].grad
+        if gine:
+            got[f"grad_edge_emb_l{l}"] = eel[l].grad
+    for n, p in ext.named_parameters():
+        got["grad_ext." + n] = p.grad
+    assert set(got) == set(r32)
     # integer bookkeeping at full size: bit-exact
     rp, perm = obk.csr_by(data.edge_index[1], N)
     assert np.array_equal(index.rowptr_dst.cpu().numpy().astype(np.int64), rp)
@@ -200,10 +185,10 @@ def test_scope_a_at_baseline_size(dev, workload):
         assert index.is_undirected == und
         if und:
             assert np.array_equal(index.rev.cpu().numpy().astype(np.int64), obk.reverse_edge_perm(data.edge_index, N))
-            assert torch.equal(got["ea"][:, 0], got["ea"][index.rev.long(), 0])       # symmetrised attention is symmetric
-    for k in ("att", "ea", "out0"):
+            assert torch.equal(got["edge_att"][:, 0], got["edge_att"][index.rev.long(), 0])       # symmetrised attention is symmetric
+    for k in ("att_log_logits", "att", "edge_att") + tuple(f"out_l{l}" for l in range(L)):
         close(got[k], r32[k], ref64=r64[k], what=k)
-    for k in ("demb", "dx0", "dW1", "dW3"):
+    for k in sorted(set(got) - {"att_log_logits", "att", "edge_att"} - {f"out_l{l}" for l in range(L)}):
         close(got[k], r32[k], 1e-4, ref64=r64[k], what=k)
 
 

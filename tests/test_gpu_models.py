@@ -275,11 +275,19 @@ def test_hipgraph_capture_of_a_training_step(dev):
         from tests.util import assert_no_memset_nodes, capture_with_dump
         graph, dot = capture_with_dump(step)
         assert_no_memset_nodes(dot, "captured GSAT training step")       # neither libgsat_hip nor the torch ops of the step may add one
+        from dp_gsat_amd.ops import device_seed_state
+        state0 = device_seed_state(dev).clone()
         res = []
         for _ in range(3):
             graph.replay()
             torch.cuda.synchronize()
             res.append((out["att"].clone(), out["loss"].clone(), out["g"].clone()))
+        # the first replay reproduces the eager result for the same seed word: rewind the device seed stream, run the step eagerly
+        device_seed_state(dev).copy_(state0)
+        step()
+        torch.cuda.synchronize()
+        for what, x, y in zip(("att", "loss", "grad W1"), (out["att"], out["loss"], out["g"]), res[0]):
+            assert torch.equal(x, y), f"eager step != first replay: {what}"
     finally:
         G.set_sync_free(False)
     for att, loss, g in res:
