@@ -127,6 +127,22 @@ __device__ __forceinline__ void st4_nt(float* p, float4 v) {
     v4f t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
 }
+// 16-byte access at a 32-bit BYTE offset from a wave-uniform base: the base stays in scalar registers and the address costs one
+// 32-bit VALU operation instead of a 64-bit multiply-add per access (the caller guarantees the offset fits: window-local rows)
+__device__ __forceinline__ float4 ld4_off(const float* base, uint32_t byte_off) {
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+__device__ __forceinline__ void st4_off(float* base, uint32_t byte_off, float4 v) {
+    *reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off) = v;
+}
+// LDS stores through an explicitly LDS-qualified pointer: next to a global store in the other arm of a branch they stay ds_write
+// (through generic pointers the compiler merges the two arms into ONE flat store with a selected address)
+__device__ __forceinline__ void st4_lds(float4* p, float4 v) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    v4f t = {v.x, v.y, v.z, v.w};
+    *(__attribute__((address_space(3))) v4f*)p = t;
+}
+__device__ __forceinline__ void st1_lds(float* p, float v) { *(__attribute__((address_space(3))) float*)p = v; }
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 f4fma(float a, float4 x, float4 acc) {
     acc.x = fmaf(a, x.x, acc.x); acc.y = fmaf(a, x.y, acc.y);

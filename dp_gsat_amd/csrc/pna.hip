@@ -652,8 +652,10 @@ __global__ __launch_bounds__(PNA_BLOCK, HAS_EE ? 2 : 4) void k_pna_bwd_dst(
 //   trip 3  the gathered x_j row of every edge -> LDS by LDS-DMA with a per-lane source address, and the attention of every edge
 //   rows    a lane group per destination row: statistics and first-occurrence args from LDS; as soon as the fold has consumed the
 //           gradient row the next one is requested into the same registers; the per-edge gradient row is written IN PLACE over
-//           the gathered row in LDS; dx_self -> dx
-//   sums    a lane group per source row: dx[j] += its edges' rows in by-source slot order, indices and rows straight from LDS
+//           the gathered row in LDS; dx_self -> dx, except for the lane group's LAST row, which stays in registers
+//   sums    a lane group per source row, the same thread <-> row map as above: dx[j] = dx_self (read back for the earlier rows, whose
+//           store the later rows have long covered; from the registers for the last one, whose store-then-load nothing would hide)
+//           + dx_add + its edges' rows in by-source slot order, indices and rows straight from LDS: the one write of dx[j]
 // Edges whose source lies outside the window (or beyond the LDS edge capacity: hub rows) spill their row to dmsg and are
 // added by k_pna_bwd_spill afterwards, in by-source slot order as well, so the result is bitwise reproducible.
 constexpr int TILE_BLOCK = 512;
@@ -694,7 +696,7 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
     float4* erow = smem4;                                        // [TE][LPR] gathered x_j row, then the edge's gradient row
     int* s_col = reinterpret_cast<int*>(erow + (size_t)TE * LPR);
     int* s_eid = s_col + TE;
-    float* s_w = reinterpret_cast<float*>(s_eid);                // NATT: [TE] the edge weight att[row] * att[source]; once its row is done, the source's share of d node_att
+    float* s_w = reinterpret_cast<float*>(s_eid);                // NATT: [TE] the source's share of d node_att of the edges kept in LDS (written by the row loop)
     float* s_att = reinterpret_cast<float*>(s_eid + TE);
     int* s_slot = reinterpret_cast<int*>(s_att + TE);            // [TE] by-source slots of the window's sources -> window-local by-destination slot
     int* s_rp = s_slot + TE;                                     // [RCAP+1] by-destination row pointers relative to the window's first slot
@@ -714,17 +716,22 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
     const int k0 = d0.y, ne = min(d1.y - k0, TE);
     const int s0 = d0.z, ns = d1.z - s0, nsl = min(ns, TE);
     // ---- trip 2 ------------------------------------------------------------------------------------------
+    // rows are addressed by a 32-bit byte offset from the window's first row (wave-uniform bases in scalar registers): a window holds at
+    // most RCAP rows of NSEG * H floats, far below 4 GiB, whatever N is
     float4 dcur[NSEG];
     float4 xi_cur = f4zero();
-    const size_t out_stride = (size_t)NSEG * H;
-    int row = lg.grp >= 0 ? n0 + grp : n1;               // idle lanes own no row
+    const uint32_t hb = (uint32_t)H * 4u, gb = NSEG * hb, cb = (uint32_t)c * 4u;      // bytes of a row of x / of the gradient, of this lane's column
+    const float* gwin = dout + (size_t)n0 * NSEG * H;
+    const float* xwin = x + (size_t)n0 * H;
+    float* dxwin = dx + (size_t)n0 * H;
+    float* mwin = dmsg + (size_t)k0 * H;
+    int r = lg.grp >= 0 ? grp : nr;                      // window-local row; idle lanes own no row
 #pragma unroll
     for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = f4zero();
-    if (row < n1 && on) {
-        const float* g0 = dout + (size_t)row * out_stride + c;
+    if (r < nr && on) {
 #pragma unroll
-        for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4(g0 + (size_t)sg * H);
-        xi_cur = ld4(x + (size_t)row * H + c);
+        for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4_off(gwin, r * gb + sg * hb + cb);
+        xi_cur = ld4_off(xwin, r * hb + cb);
     }
     for (int i = tid; i <= nr; i += TILE_BLOCK) {
         s_rp[i] = rowptr[n0 + i] - k0;
@@ -745,12 +752,8 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
                                              (__attribute__((address_space(3))) void*)(erow + (size_t)(base + wave * RPW) * LPR), 16, 0, 0);
     }
     for (int i = tid; i < ne; i += TILE_BLOCK) {
-        if (NATT) {              // att[source] for the gradient, the edge weight for everything else: the slot's row by bisection of the row pointers
-            int lo = 0, hi = nr;
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_rp[mid] <= i) lo = mid; else hi = mid; }
-            const float a = att[s_col[i]];
-            s_att[i] = a;
-            s_w[i] = a * s_na[lo];
+        if (NATT) {              // att[source]; the edge weight att[source] * att[row] is formed by the row's own lane group
+            s_att[i] = att[s_col[i]];
         } else {
             s_att[i] = att ? att[s_eid[i]] : 1.f;
         }
@@ -758,9 +761,11 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // ---- destination rows ----------------------------------------------------------------------------------
-    for (; row < n1; row += GPB) {
-        const int nrow = row + GPB;
-        const int beg = s_rp[row - n0], end = s_rp[row - n0 + 1];
+    float4 dx_keep = f4zero();                                   // dx_self of the lane group's LAST row: it never leaves the registers
+    for (; r < nr; r += GPB) {
+        const int nr_ = r + GPB;                                 // the lane group's next row
+        const int beg = s_rp[r], end = s_rp[r + 1];
+        const float na_row = NATT ? s_na[r] : 0.f;
         const float cnt = (float)(end - beg);
         // pass 1: statistics and first-occurrence args (empty rows fall through with zero statistics)
         float sa = 0.f, sa2 = 0.f, amin = INFINITY, amax = -INFINITY;
@@ -769,25 +774,30 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
         aj.init();
         int4 jmin = make_int4(beg, beg, beg, beg), jmax = jmin;
         float wfirst = 1.f;
-        for (int k = beg; k < end; ++k) {
-            float w;
-            float4 xv;
-            if (k < ne) {
-                w = NATT ? s_w[k] : s_att[k];
-                xv = on ? erow[(size_t)k * LPR + lane] : f4zero();
-            } else {                                             // beyond the LDS edge capacity (hub rows): straight from memory
-                w = NATT ? att[col[k0 + k]] * s_na[row - n0] : (att ? att[eid[k0 + k]] : 1.f);
-                xv = on ? ld4(x + (size_t)col[k0 + k] * H + c) : f4zero();
-            }
+        // slots [beg, mid) lie in LDS, [mid, end) beyond its edge capacity (hub rows): two loops over one body, so that the common loop
+        // carries neither the per-edge branch nor the wait on the rare loop's global loads
+        const int mid = min(end, max(beg, ne));
+        auto stats = [&](int k, float w, float4 xv) {
             if (k == beg) wfirst = w;
             sa += w; sa2 = fmaf(w, w, sa2);
             if (w < amin) { amin = w; kmin_a = k; }
             if (w > amax) { amax = w; kmax_a = k; }
             const float4 m = f4scale(w, xv);
-            if (m.x < aj.mn.x) jmin.x = k; if (m.y < aj.mn.y) jmin.y = k; if (m.z < aj.mn.z) jmin.z = k; if (m.w < aj.mn.w) jmin.w = k;
-            if (m.x > aj.mx.x) jmax.x = k; if (m.y > aj.mx.y) jmax.y = k; if (m.z > aj.mx.z) jmax.z = k; if (m.w > aj.mx.w) jmax.w = k;
-            aj.add(m);
-        }
+            // the running extremes only decide the first-occurrence args here, so they follow the SAME compare by a select (fminf /
+            // fmaxf would re-canonicalise the accumulator every edge; the two differ in the sign of a zero extreme at most, which no
+            // later compare can see)
+#define GSAT_TARG(C)                                                                                                       \
+            if (m.C < aj.mn.C) { jmin.C = k; aj.mn.C = m.C; }                                                              \
+            if (m.C > aj.mx.C) { jmax.C = k; aj.mx.C = m.C; }
+            GSAT_TARG(x) GSAT_TARG(y) GSAT_TARG(z) GSAT_TARG(w)
+#undef GSAT_TARG
+            aj.s.x += m.x; aj.s.y += m.y; aj.s.z += m.z; aj.s.w += m.w;
+            aj.q.x = fmaf(m.x, m.x, aj.q.x); aj.q.y = fmaf(m.y, m.y, aj.q.y); aj.q.z = fmaf(m.z, m.z, aj.q.z); aj.q.w = fmaf(m.w, m.w, aj.q.w);
+        };
+        for (int k = beg; k < mid; ++k)
+            stats(k, NATT ? s_att[k] * na_row : s_att[k], on ? erow[(size_t)k * LPR + lane] : f4zero());
+        for (int k = mid; k < end; ++k)                          // straight from memory
+            stats(k, NATT ? att[col[k0 + k]] * na_row : (att ? att[eid[k0 + k]] : 1.f), on ? ld4(x + (size_t)col[k0 + k] * H + c) : f4zero());
         const float4 xi = xi_cur;
         const Acc4 ai = self_stats(xi, sa, sa2, amin, amax);
         const float n = fmaxf(cnt, 1.f), inv_n = 1.f / n;
@@ -813,15 +823,6 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
             P = make_float4(p0.x - mean.x * Q.x, p0.y - mean.y * Q.y, p0.z - mean.z * Q.z, p0.w - mean.w * Q.w);           \
         }
         GSAT_TFOLD(ai, 0, Pi, Qi, gmn_i, gmx_i)
-        GSAT_TFOLD(aj, 1, Pj, Qj, gmn_j, gmx_j)
-#undef GSAT_TFOLD
-        // the gradient row is consumed: request the next one into the same registers, in flight under the rest of this row
-        if (nrow < n1 && on) {
-            const float* g0 = dout + (size_t)nrow * out_stride + c;
-#pragma unroll
-            for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4(g0 + (size_t)sg * H);
-            xi_cur = ld4(x + (size_t)nrow * H + c);
-        }
         if (on) {      // x_i third in closed form (see k_pna_bwd_dst); an empty row gets exact zeros (P = Q = 0 * finite, sums 0)
             float4 dxi;
 #define GSAT_TSELF(C)                                                                                                      \
@@ -837,24 +838,24 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
             GSAT_TSELF(x) GSAT_TSELF(y) GSAT_TSELF(z) GSAT_TSELF(w)
 #undef GSAT_TSELF
             if (end == beg) dxi = f4zero();                      // amin/amax are +-inf on an empty row: no in-edges, no gradient
-            st4(dx + (size_t)row * H + c, dxi);
+            // earlier rows wait in dx for the per-source pass (the store is long done by then); the last row, whose round trip through
+            // memory nothing would hide, stays in registers
+            if (nr_ < nr) st4_off(dxwin, r * hb + cb, dxi); else dx_keep = dxi;
+        }
+        // the x_j half is folded after the self part, so that the self part's coefficients are dead by then; the gradient row is
+        // consumed: request the next one into the same registers, in flight under the rest of this row
+        GSAT_TFOLD(aj, 1, Pj, Qj, gmn_j, gmx_j)
+#undef GSAT_TFOLD
+        if (nr_ < nr && on) {
+#pragma unroll
+            for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4_off(gwin, nr_ * gb + sg * hb + cb);
+            xi_cur = ld4_off(xwin, nr_ * hb + cb);
         }
         // pass 2: per-edge gradient rows, in place over the gathered rows
-        for (int k = beg; k < end; ++k) {
-            float w;
-            float4 xj;
-            int e = 0, j;
-            if (k < ne) {
-                w = NATT ? s_w[k] : s_att[k]; j = s_col[k];
-                if (!NATT) e = s_eid[k];
-                xj = on ? erow[(size_t)k * LPR + lane] : f4zero();
-            } else {
-                j = col[k0 + k];
-                if (!NATT) e = eid[k0 + k];
-                w = NATT ? att[j] * s_na[row - n0] : (att ? att[e] : 1.f);
-                xj = on ? ld4(x + (size_t)j * H + c) : f4zero();
-            }
-            const bool in_lds = k < ne && j >= n0 && j < n1;
+        float dna_acc = 0.f;                                     // NATT: the row's share (as destination) of d node_att
+        // a_src: NATT, att[source]; e: the edge id (edge attention); lds: the slot lies in LDS
+        auto grad = [&](int k, float w, float a_src, int j, int e, float4 xj, bool lds) {
+            const bool in_lds = lds && j >= n0 && j < n1;
             float da = 0.f;
             if (on) {
                 float4 dm;
@@ -863,32 +864,45 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
                 dm.z = fmaf(Qj.z, w * xj.z, Pj.z) + (k == jmin.z ? gmn_j.z : 0.f) + (k == jmax.z ? gmx_j.z : 0.f);
                 dm.w = fmaf(Qj.w, w * xj.w, Pj.w) + (k == jmin.w ? gmn_j.w : 0.f) + (k == jmax.w ? gmx_j.w : 0.f);
                 const float4 o = f4scale(w, dm);
-                if (in_lds) erow[(size_t)k * LPR + lane] = o; else st4(dmsg + (size_t)(k0 + k) * H + c, o);
+                if (in_lds) st4_lds(erow + (size_t)k * LPR + lane, o);
+                else if (lds) st4_off(mwin, k * hb + cb, o);                      // k < TE: the offset is window-local
+                else st4(dmsg + (size_t)(k0 + k) * H + c, o);
                 da = f4dot(dm, xj) + t1 + w * t2 + (k == kmin_a ? tmn : 0.f) + (k == kmax_a ? tmx : 0.f);
             }
             if (datt) {
                 da = group_sum<LPR>(da);
                 if (NATT) {
                     if (lane == 0) {
-                        s_dna[row - n0] = fmaf(da, k < ne ? s_att[k] : att[j], s_dna[row - n0]);      // destination share: d w * att[source]
-                        const float share = da * s_na[row - n0];                                      // source share: d w * att[row]
-                        if (in_lds) s_w[k] = share; else dw[k0 + k] = share;                          // (the slot's weight is not read again)
+                        dna_acc = fmaf(da, a_src, dna_acc);                                           // destination share: d w * att[source]
+                        const float share = da * na_row;                                              // source share: d w * att[row]
+                        if (in_lds) st1_lds(s_w + k, share); else dw[k0 + k] = share;
                     }
                 } else if (lane == 0) datt[e] = da;
             }
+        };
+        for (int k = beg; k < mid; ++k) {
+            const float a = s_att[k];
+            grad(k, NATT ? a * na_row : a, a, s_col[k], NATT ? 0 : s_eid[k], on ? erow[(size_t)k * LPR + lane] : f4zero(), true);
         }
+        for (int k = mid; k < end; ++k) {
+            const int j = col[k0 + k], e = NATT ? 0 : eid[k0 + k];
+            const float a = NATT ? att[j] : (att ? att[e] : 1.f);
+            grad(k, NATT ? a * na_row : a, a, j, e, on ? ld4(x + (size_t)j * H + c) : f4zero(), false);
+        }
+        if (NATT && datt && lane == 0) s_dna[r] = dna_acc;
     }
     __syncthreads();
     // ---- per-source sums over the rows kept in LDS (same lane group <-> row map as above: dx[j] is this thread's own store) ----
-    for (int j = lg.grp >= 0 ? n0 + grp : n1; j < n1; j += GPB) {
+    const float* awin = dx_add ? dx_add + (size_t)n0 * H : nullptr;
+    for (int j = lg.grp >= 0 ? grp : nr; j < nr; j += GPB) {
         if (!on) continue;
-        const int sb = s_rps[j - n0], se = s_rps[j - n0 + 1];
-        float4 acc = ld4(dx + (size_t)j * H + c);
+        const int sb = s_rps[j], se = s_rps[j + 1];
+        float4 acc = j + GPB < nr ? ld4_off(dxwin, j * hb + cb) : dx_keep;
         // NATT, datt_acc: d node_att is shared by every layer that used the attention: this launch adds its share to what is there
-        const float dprev = (NATT && datt && datt_acc && lane == 0) ? datt[j] : 0.f;
-        if (dx_add) {              // a gradient that reaches x by another path (the layer's residual): added here instead of by a separate kernel
-            const float4 r = ld4(dx_add + (size_t)j * H + c);
-            acc.x += r.x; acc.y += r.y; acc.z += r.z; acc.w += r.w;
+        const float dprev = (NATT && datt && datt_acc && lane == 0) ? datt[n0 + j] : 0.f;
+        if (awin) {                // a gradient that reaches x by another path (the layer's residual): added here instead of by a separate kernel
+            const float4 ra = ld4_off(awin, j * hb + cb);
+            acc.x += ra.x; acc.y += ra.y; acc.z += ra.z; acc.w += ra.w;
         }
         float sw = 0.f;
         for (int s_ = sb; s_ < se; ++s_) {
@@ -896,11 +910,11 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
             if (kl >= 0 && kl < ne) {
                 const float4 v = erow[(size_t)kl * LPR + lane];
                 acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-                if (NATT) sw += s_w[kl];
+                if (NATT && datt) sw += s_w[kl];             // (the slots hold shares only when the gradient is asked for)
             }
         }
-        st4(dx + (size_t)j * H + c, acc);
-        if (NATT && datt && lane == 0) datt[j] = (s_dna[j - n0] + sw) + dprev;      // destination share (this lane's own LDS store of the row loop) + source share
+        st4_off(dxwin, j * hb + cb, acc);
+        if (NATT && datt && lane == 0) datt[n0 + j] = (s_dna[j] + sw) + dprev;      // destination share (this lane's own LDS store of the row loop) + source share
     }
 }
 
