@@ -7,14 +7,14 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgsat_hip.so")
 
-P, I64, I32, F32, SZ, INT, U64 = c_void_p, c_int64, c_int32, c_float, c_size_t, c_int, c_uint64
+P, I64, I32, F32, F64, SZ, INT, U64 = c_void_p, c_int64, c_int32, c_float, c_double, c_size_t, c_int, c_uint64
 
 # name -> (restype, argtypes); must list every symbol of include/gsat_hip.h (tests check this).
 SIGNATURES = {
@@ -94,6 +94,13 @@ SIGNATURES = {
     "gsat_und_line_graph": (INT, [P, P, P, P, P, I64, I64, P, P]),
     "gsat_segment_pool_fwd": (INT, [P, P, I64, I64, INT, P, P]),
     "gsat_segment_pool_bwd": (INT, [P, P, I64, I64, INT, P, P]),
+    "gsat_rank_edges_lds_cap": (I64, []),
+    "gsat_rank_edges_workspace_bytes": (SZ, [I64]),
+    "gsat_rank_edges": (INT, [P, P, P, P, I64, I64, I64, I64, INT, P, P, P, P, P, SZ, P]),
+    "gsat_auroc_workspace_bytes": (SZ, [I64]),
+    "gsat_auroc": (INT, [P, P, I64, P, P, SZ, P]),
+    "gsat_delta_kl_workspace_bytes": (SZ, [I64]),
+    "gsat_delta_kl": (INT, [P, P, I64, F64, P, P, SZ, P]),
 }
 
 

@@ -1,0 +1,204 @@
+"""Explanation metrics on the device: per-graph edge ranking, precision@k, attention ROC-AUC, delta-KL.
+
+The reference scores the edge attention against ground-truth edge labels after every batch on the host
+(src/run_gsat.py:656-668): ``att.data.cpu()``, a Python loop over graphs with two boolean masks over all E edges, a host
+``argsort`` and an ``.item()`` per graph (get_precision_at_k, :783-791), sklearn's ``roc_auc_score`` (:763) and get_delta_kl
+(:793-800).  Here the same numbers come from HIP kernels (csrc/explain.hip) on the attention where it already lives; nothing is
+copied to the host until :meth:`ExplanationMeter.compute`.
+
+Tie rule (the contract of every ranking here): higher attention first, equal attention -> LOWER EDGE ID first, -0.0 == +0.0.  The
+reference's ``np.argsort(-att)[:k]`` is an unstable sort, i.e. ambiguous under ties -- and ties are the rule in edge-attention mode,
+where the symmetrised mask gives an edge and its reverse the same value.  NaN attention is unsupported.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import _lib, ops
+from ._lib import GsatHipError, call, ptr, stream
+from .graph_index import call_size, get_index
+
+_PATHS = {"auto": 0, "fused": 1, "general": 2}
+
+
+class EdgeRanking(NamedTuple):
+    """order int32[E]: edge ids graph by graph, best first (``order[edge_ptr[g] + r]`` = rank-r edge of graph g); rank int32[E]:
+    position of edge e inside its graph; edge_ptr int32[G+1]."""
+    order: torch.Tensor
+    rank: torch.Tensor
+    edge_ptr: torch.Tensor
+
+
+def _att(att) -> torch.Tensor:
+    att = ops.edge_tensor(att)
+    if not isinstance(att, torch.Tensor) or not att.is_cuda:
+        raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    if att.dim() > 2 or (att.dim() == 2 and att.shape[1] != 1):
+        raise ValueError("attention must have shape [E] or [E, 1]")
+    return att.detach().reshape(-1).to(torch.float32).contiguous()
+
+
+def _labels(exp_labels, E: int) -> torch.Tensor:
+    if not isinstance(exp_labels, torch.Tensor) or not exp_labels.is_cuda:
+        raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    lab = exp_labels.reshape(-1)
+    if lab.shape[0] != E:
+        raise ValueError(f"exp_labels has {lab.shape[0]} entries for {E} edges")
+    if lab.dtype == torch.uint8:                 # the kernels read "nonzero = labelled" themselves
+        return lab.contiguous()
+    return lab.contiguous().view(torch.uint8) if lab.dtype == torch.bool else (lab != 0).to(torch.uint8)
+
+
+def _segments(edge_index, batch, num_graphs):
+    if not edge_index.is_cuda or not batch.is_cuda:
+        raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    return get_index(edge_index, int(batch.shape[0])).graphs(batch, num_graphs)
+
+
+def _rank(att, edge_index, batch, num_graphs, path, k=0, label=None, want=("order", "rank")):
+    """One gsat_rank_edges call; returns (dict of the wanted outputs, GraphSegments)."""
+    if path not in _PATHS:
+        raise ValueError(f"path must be one of {sorted(_PATHS)}")
+    a = _att(att)
+    seg = _segments(edge_index, batch, num_graphs)
+    E, G, dev = seg.index.E, seg.G, a.device
+    if a.shape[0] != E:
+        raise ValueError(f"attention has {a.shape[0]} entries for {E} edges")
+    eptr, eorder = seg.edge_segments[:2]
+    lab = _labels(label, E) if label is not None else None
+    out = {}
+    if "order" in want:
+        out["order"] = torch.empty(E, dtype=torch.int32, device=dev)
+    if "rank" in want:
+        out["rank"] = torch.empty(E, dtype=torch.int32, device=dev)
+    if "topk" in want:
+        out["topk"] = torch.empty(E, dtype=torch.uint8, device=dev)
+    if "hits" in want:
+        out["hits"] = torch.empty(G, dtype=torch.int32, device=dev)
+    max_seg = seg.max_edges_per_graph                      # -1: unknown and not to be read back now -> general path
+    code = _PATHS[path]
+    fused = code == 1 or (code == 0 and 0 <= max_seg <= rank_edges_lds_cap())
+    ws, ws_bytes = None, 0
+    if not fused:
+        ws_bytes = call_size("gsat_rank_edges_workspace_bytes", E)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    call("gsat_rank_edges", ptr(a) if E else None, ptr(eptr), ptr(eorder) if E else None, ptr(lab) if lab is not None and E else None,
+         E, G, int(k), int(max_seg), code, *(ptr(out[n]) if n in out and out[n].numel() else None for n in ("order", "rank", "topk")),
+         ptr(out["hits"]) if "hits" in out and G and lab is not None and E else None, ptr(ws), ws_bytes, stream())
+    if "hits" in out and (E == 0 or lab is None):
+        out["hits"].zero_()
+    return out, seg
+
+
+def rank_edges_lds_cap() -> int:
+    """Largest graph (in edges) the fused ranking kernel sorts; larger graphs take the general (radix sort) path."""
+    return int(_lib.load().gsat_rank_edges_lds_cap())
+
+
+def rank_edges(att, edge_index, batch, num_graphs: Optional[int] = None, path: str = "auto") -> EdgeRanking:
+    """Every graph's edges in descending attention order (ties: lower edge id first).  ``path``: "auto" (fused kernel when the
+    largest graph fits it), "fused" (raises GsatHipError when it does not) or "general"."""
+    out, seg = _rank(att, edge_index, batch, num_graphs, path)
+    return EdgeRanking(out["order"], out["rank"], seg.edge_segments[0])
+
+
+def topk_edge_mask(att, edge_index, batch, k: Optional[int] = None, ratio: Optional[float] = None, num_graphs: Optional[int] = None,
+                   path: str = "auto") -> torch.Tensor:
+    """bool[E]: the ``k`` best edges of every graph, or its ``ceil(ratio * E_g)`` best."""
+    if (k is None) == (ratio is None):
+        raise ValueError("give exactly one of k and ratio")
+    if k is not None:
+        out, _ = _rank(att, edge_index, batch, num_graphs, path, k=k, want=("topk",))
+        return out["topk"].bool()
+    out, seg = _rank(att, edge_index, batch, num_graphs, path, want=("rank",))
+    eptr, _, eg, _ = seg.edge_segments
+    keep = torch.ceil((eptr[1:] - eptr[:-1]).double() * float(ratio)).to(torch.int32)
+    return out["rank"] < keep[eg]
+
+
+def precision_at_k(att, exp_labels, k: int, batch, edge_index, num_graphs: Optional[int] = None, path: str = "auto") -> torch.Tensor:
+    """float32[G] on the device: labelled edges among each graph's ``k`` best, divided by ``k`` -- also for a graph with fewer
+    than ``k`` edges (src/run_gsat.py:790).  Argument order of the reference's get_precision_at_k."""
+    if int(k) <= 0:
+        raise ValueError("k must be positive")
+    out, _ = _rank(att, edge_index, batch, num_graphs, path, k=k, label=exp_labels, want=("hits",))
+    # int / k correctly rounded to fp32: a float32 tensor divided by a Python scalar is a multiplication by the rounded reciprocal
+    # on the device (15 / 100 -> 0.14999999), so the quotient is formed in fp64 and rounded once
+    return (out["hits"].to(torch.float64) / float(k)).to(torch.float32)
+
+
+def attention_auroc_counts(att, exp_labels) -> torch.Tensor:
+    """int64[3] on the device: (U2, P, Nn) with P / Nn the numbers of labelled / unlabelled edges and
+    U2 = sum over labelled edges of (2 * unlabelled edges with lower attention + unlabelled edges with equal attention);
+    ROC-AUC = U2 / (2 P Nn).  Integer arithmetic: bitwise repeatable."""
+    a = _att(att)
+    E = a.shape[0]
+    lab = _labels(exp_labels, E)
+    out = torch.empty(3, dtype=torch.int64, device=a.device)
+    ws_bytes = call_size("gsat_auroc_workspace_bytes", E)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    call("gsat_auroc", ptr(a) if E else None, ptr(lab) if E else None, E, ptr(out), ptr(ws), ws_bytes, stream())
+    return out
+
+
+def attention_auroc(att, exp_labels) -> torch.Tensor:
+    """Exact tie-aware ROC-AUC of the attention against binary edge labels: a 0-dim float64 device tensor; 0.0 when only one
+    class is present (src/run_gsat.py:761-763)."""
+    c = attention_auroc_counts(att, exp_labels)
+    den = 2 * c[1] * c[2]
+    return torch.where(den > 0, c[0].double() / den.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=c.device))
+
+
+def delta_kl_stats(att, exp_labels, eps: float = 1e-6) -> torch.Tensor:
+    """float32[3] on the device: (delta_kl, mean attention of labelled edges, mean attention of unlabelled edges); the mean of an
+    empty class is 0."""
+    a = _att(att)
+    E = a.shape[0]
+    lab = _labels(exp_labels, E)
+    out = torch.empty(3, dtype=torch.float32, device=a.device)
+    ws_bytes = call_size("gsat_delta_kl_workspace_bytes", E)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    call("gsat_delta_kl", ptr(a) if E else None, ptr(lab) if E else None, E, float(eps), ptr(out), ptr(ws), ws_bytes, stream())
+    return out
+
+
+def delta_kl(att, exp_labels, eps: float = 1e-6) -> torch.Tensor:
+    """The reference's get_delta_kl (src/run_gsat.py:793-800) as a 0-dim float32 device tensor."""
+    return delta_kl_stats(att, exp_labels, eps)[0]
+
+
+class ExplanationMeter:
+    """Device twin of the accumulation in dual_run_one_epoch (src/run_gsat.py:646-678).  ``update`` launches kernels and keeps device
+    copies, never syncing (given ``data.num_graphs``); ``compute`` scores everything seen -- one global ROC-AUC, the mean of the per-graph precisions, the mean of
+    the per-batch delta_kl, the mean attention of labelled / unlabelled edges -- with ONE host read at the very end."""
+
+    def __init__(self, k: int):
+        if int(k) <= 0:
+            raise ValueError("k must be positive")
+        self.k = int(k)
+        self.reset()
+
+    def reset(self):
+        self._att, self._lab, self._prec, self._dkl = [], [], [], []
+
+    def update(self, att, data) -> None:
+        """``data``: a collated batch with ``edge_index``, ``batch``, ``edge_label`` and ``num_graphs``.  Without ``num_graphs`` the graph
+        count is read back from ``batch.max()`` once per batch -- the only sync ``update`` can cause."""
+        a = _att(att)
+        lab = _labels(data.edge_label, a.shape[0])
+        self._prec.append(precision_at_k(a, lab, self.k, data.batch, data.edge_index, getattr(data, "num_graphs", None)))
+        self._dkl.append(delta_kl(a, lab))
+        self._att.append(a.clone())
+        self._lab.append(lab.clone())            # like the attention: the caller may refill its (static) buffers between batches
+
+    def compute(self) -> dict:
+        if not self._att:
+            raise ValueError("ExplanationMeter.compute() before any update()")
+        a, lab = torch.cat(self._att), torch.cat(self._lab)
+        means = delta_kl_stats(a, lab)[1:].double()
+        vals = torch.cat([attention_auroc(a, lab).view(1), torch.cat(self._prec).double().mean().view(1),
+                          torch.stack(self._dkl).double().mean().view(1), means]).tolist()          # the one host read
+        return {"att_auroc": vals[0], f"precision@{self.k}": vals[1], "delta_kl": vals[2],
+                "avg_signal_att_weights": vals[3], "avg_bkg_att_weights": vals[4]}

@@ -376,6 +376,7 @@ class GraphSegments:
         call("gsat_segment_ptr32", ptr(self.batch), n, self.G, ptr(self.node_ptr), ptr(self.node_seg32), ptr(flags), stream())
         self._flags = flags
         self._edge = None
+        self._max_edges = None
 
     def check(self):
         self.index._checked = False
@@ -400,6 +401,18 @@ class GraphSegments:
             call("gsat_narrow_i64", ptr(eg), E, ptr(eg32), stream())
             self._edge = (eptr, order, eg, eg32)
         return self._edge
+
+
+    @property
+    def max_edges_per_graph(self) -> int:
+        """Edge count of the largest graph (by ``edge_segments``): one small read-back per batch, cached.  -1 while it is unknown and
+        must not be read -- sync-free mode, or during stream capture."""
+        if self._max_edges is None:
+            if _SYNC_FREE or torch.cuda.is_current_stream_capturing():
+                return -1
+            eptr = self.edge_segments[0]
+            self._max_edges = int((eptr[1:] - eptr[:-1]).max().item()) if self.G > 0 else 0
+        return self._max_edges
 
 
 def call_size(name, *args) -> int:

@@ -606,6 +606,51 @@ int gsat_segment_pool_fwd(const float* x, const int32_t* ptr, int64_t num_segmen
 int gsat_segment_pool_bwd(const float* dout, const int32_t* ptr, int64_t num_segments, int64_t H,
                           int mean, float* dx, void* stream);
 
+/* ================================== explanation metrics ===================================== */
+
+/*
+ * Per-graph ranking of the edges by attention.  replaces: the per-graph host loop of get_precision_at_k
+ * (src/run_gsat.py:783-791: two boolean masks over all E edges, a host argsort and an .item() per graph).
+ * TOTAL ORDER (both paths): higher attention first; equal attention -> lower edge id first; -0.0 counts as +0.0.  NaN attention is
+ * unsupported (its position is unspecified).  The reference's np.argsort(-att)[:k] is unstable, i.e. ambiguous under ties.
+ * att fp32[E]; edge_ptr int32[G+1] / edge_order int32[E]: the edges grouped by graph (a permutation of [0, E));
+ * label uint8[E] nullable (nonzero = explanation edge; required when hits is asked for); k >= 0.
+ * Outputs, each nullable: order int32[E] (edge ids, graph by graph, best first: order[edge_ptr[g] + r] is the rank-r edge of graph g),
+ * rank int32[E] (position of edge e inside its graph), topk uint8[E] (1 iff rank < k), hits int32[G] (labelled edges among the
+ * first min(k, E_g) of graph g).
+ * max_seg_edges: an upper bound of the edges of one graph, -1 = unknown.  path: 0 = auto (fused iff 0 <= max_seg_edges <=
+ * gsat_rank_edges_lds_cap(), else general), 1 = fused (GSAT_ERR_ARG when the bound is unknown or above the cap: never a truncation),
+ * 2 = general.  Fused: ONE launch, no workspace; graphs of <= 64 edges are sorted by one wavefront in registers, larger ones by one
+ * workgroup in LDS; a graph that exceeds a wrong max_seg_edges (or whose
+ * edge_ptr range is invalid) is skipped whole and gets hits = -1.  General: a stable radix sort of
+ * (graph id, attention) keys plus two small launches, any graph size; workspace gsat_rank_edges_workspace_bytes(E).
+ */
+int64_t gsat_rank_edges_lds_cap(void);
+size_t gsat_rank_edges_workspace_bytes(int64_t num_edges);
+int gsat_rank_edges(const float* att, const int32_t* edge_ptr, const int32_t* edge_order, const uint8_t* label, int64_t num_edges,
+                    int64_t num_graphs, int64_t k, int64_t max_seg_edges, int path, int32_t* order, int32_t* rank, uint8_t* topk,
+                    int32_t* hits, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Exact, tie-aware ROC-AUC of att fp32[E] against label uint8[E] (0 / 1), as three integers: out uint64[3] = (U2, P, Nn) with
+ * P / Nn the positive / negative counts and U2 = sum over positives of (2 * #negatives below + #negatives equal);
+ * AUROC = U2 / (2 * P * Nn), undefined (the caller reports 0) when P * Nn == 0.  Integer sums: bitwise repeatable.
+ * replaces: roc_auc_score(exp_labels, att) on host copies (src/run_gsat.py:761-763).
+ */
+size_t gsat_auroc_workspace_bytes(int64_t num_edges);
+int gsat_auroc(const float* att, const uint8_t* label, int64_t num_edges, uint64_t* out, void* workspace, size_t workspace_bytes,
+               void* stream);
+
+/*
+ * out fp32[3] = (delta_kl, mean attention of labelled edges, mean attention of unlabelled edges); a mean over no edge is 0.
+ * delta_kl = sum_e p log(a / r) + (1 - p) log((1 - a) / (1 - r)), a = clamp(att, eps, 1 - eps), p = clamp(label, eps, 1 - eps),
+ * r = clamp(mean(a), eps, 1 - eps); evaluated in fp64 with a fixed combine order (no float atomics: bitwise repeatable).
+ * replaces: get_delta_kl and avg_signal / avg_bkg_att_weights (src/run_gsat.py:793-800, 773-774).
+ */
+size_t gsat_delta_kl_workspace_bytes(int64_t num_edges);
+int gsat_delta_kl(const float* att, const uint8_t* label, int64_t num_edges, double eps, float* out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
