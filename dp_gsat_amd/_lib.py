@@ -101,6 +101,10 @@ SIGNATURES = {
     "gsat_auroc": (INT, [P, P, I64, P, P, SZ, P]),
     "gsat_delta_kl_workspace_bytes": (SZ, [I64]),
     "gsat_delta_kl": (INT, [P, P, I64, F64, P, P, SZ, P]),
+    "gsat_subgraph_block_items": (I64, []),
+    "gsat_subgraph_workspace_bytes": (SZ, [I64, I64]),
+    "gsat_subgraph_index": (INT, [P, I64, I64, P, P, I64, P, INT, INT, INT, I64, I64, INT, P, P, P, P, P, P, P, P, SZ, P]),
+    "gsat_gather_rows": (INT, [P, P, I64, I64, P, P]),
 }
 
 

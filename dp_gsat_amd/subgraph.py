@@ -1,0 +1,225 @@
+"""Explanation subgraphs on the device: edge / node subgraph extraction with relabelling, top-k explanation subgraphs, fidelity.
+
+The reference cuts the attended subgraph out on the host, graph by graph, after copying everything back
+(example/trainer.py:140-170: ``subgraph(node_subset.cpu(), data.edge_index.cpu(), edge_attr=batch_att)``).  Here a 0/1 mask over the
+edges (or the nodes) of a whole collated batch becomes a new collated batch in 4-6 kernel launches plus one row gather per
+attribute (csrc/subgraph.hip); kept nodes and edges stay in their original order, so the result is unique.
+
+Why a compacted graph and not a hard 0/1 ``edge_atten``: for GIN / GINE (a masked sum) the two are the same thing, for
+``PNAConvSimple`` they are not -- a message scaled by 0 still enters ``mean``, ``min``, ``max``, ``std`` and the in-degree.  Fidelity of
+a PNA model therefore needs the graph WITHOUT the edges (:func:`explanation_fidelity`).
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib, ops
+from ._lib import GsatHipError, call, ptr, stream
+from .explain import topk_edge_mask
+from .graph_index import call_size, get_index, sync_free
+from .synth import Batch
+
+_NO_CPU = "dp_gsat_amd.subgraph needs ROCm (cuda) tensors: the HIP path has no CPU fallback"
+
+
+def subgraph_block_items() -> int:
+    """Items (nodes or edges) one workgroup of the extraction kernels owns."""
+    return int(_lib.load().gsat_subgraph_block_items())
+
+
+class SubgraphBatch(Batch):
+    """The extracted batch: ``x, edge_index, batch, edge_attr, edge_label, node_label`` of the kept nodes / edges, ``y`` and
+    ``num_graphs`` unchanged (a graph that lost every node is an empty segment), plus ``node_id int64[N']`` / ``edge_id int64[E']``
+    (old ids, ascending), ``edge_mask bool[E]`` over the ORIGINAL edges, ``node_ptr int32[G+1]`` and ``counts int64[4]`` =
+    (N', E', overflow, bad id) on the device."""
+
+    def check(self) -> "SubgraphBatch":
+        """One host read of ``counts``: raises ValueError when the ``sizes`` the extraction was given were not the true sizes
+        (nothing was written beyond them) or an edge had a node id outside [0, N)."""
+        n, e, over, bad = self.counts.tolist()
+        if bad:
+            raise ValueError("edge_index contains node ids outside [0, num_nodes)")
+        if over:
+            raise ValueError(f"subgraph sizes were declared as {tuple(self.sizes)} but the extraction keeps ({n}, {e})")
+        return self
+
+    def prime(self) -> "SubgraphBatch":
+        """Register ``batch`` with ``num_graphs`` at the batch index of ``edge_index``: a model forward on this batch then returns
+        ``num_graphs`` rows also when the last graphs are empty, and never reads ``batch.max()`` back.  Done by the extraction
+        itself, except during stream capture and for an empty result."""
+        if self.num_nodes > 0 and self.num_edges > 0:
+            get_index(self.edge_index, self.num_nodes).graphs(self.batch, self.num_graphs)
+        return self
+
+
+def _need_cuda(*tensors):
+    for t in tensors:
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise GsatHipError(_NO_CPU)
+
+
+def _keep_u8(keep, n: int, what: str) -> torch.Tensor:
+    """0/1-or-nonzero uint8[n] view of a mask (bool and uint8 masks cost nothing)."""
+    keep = keep.reshape(-1)
+    if keep.shape[0] != n:
+        raise ValueError(f"{what} has {keep.shape[0]} entries for {n}")
+    if keep.dtype == torch.uint8:
+        return keep.contiguous()
+    return keep.contiguous().view(torch.uint8) if keep.dtype == torch.bool else (keep != 0).to(torch.uint8)
+
+
+def gather_rows(table: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """``table[index]`` along dim 0 for a tensor of any dtype and trailing shape (gsat_gather_rows); ``index`` int64, trusted."""
+    _need_cuda(table, index)
+    if index.dtype != torch.int64 or index.dim() != 1:
+        raise ValueError("index must be an int64 vector")
+    table = table.contiguous()
+    n = int(index.shape[0])
+    out = torch.empty((n,) + tuple(table.shape[1:]), dtype=table.dtype, device=table.device)
+    row_bytes = table.element_size()
+    for s in table.shape[1:]:
+        row_bytes *= int(s)
+    if n and row_bytes:
+        call("gsat_gather_rows", ptr(table), ptr(index.contiguous()), n, row_bytes, ptr(out), stream())
+    return out
+
+
+def _extract(data, keep: torch.Tensor, mode: int, drop_isolated: bool, sizes: Optional[Sequence[int]]) -> SubgraphBatch:
+    x, edge_index, batch = data.x, data.edge_index, data.batch
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    N, E, dev = int(x.shape[0]), int(edge_index.shape[1]), edge_index.device
+    if batch.dtype != torch.int64 or batch.dim() != 1 or int(batch.shape[0]) != N:
+        raise ValueError("batch must be an int64 vector with one entry per node")
+    if keep.numel() != (E if mode == 0 else N):
+        raise ValueError(f"{'edge_keep' if mode == 0 else 'node_keep'} has {keep.numel()} entries for {E if mode == 0 else N}")
+    _need_cuda(x, edge_index, batch, keep)
+    keep = _keep_u8(keep, E if mode == 0 else N, "edge_keep" if mode == 0 else "node_keep")
+    capturing = torch.cuda.is_current_stream_capturing()
+    if sizes is None and (sync_free() or capturing):
+        raise ValueError("edge_subgraph / node_subgraph read the sizes of the result back once; in sync-free mode or during "
+                         "stream capture pass sizes=(num_nodes, num_edges) of the result instead")
+    if sizes is not None:
+        sizes = (int(sizes[0]), int(sizes[1]))
+        if not (0 <= sizes[0] <= N and 0 <= sizes[1] <= E):
+            raise ValueError(f"sizes {sizes} outside (0..{N}, 0..{E})")
+    seg = get_index(edge_index, N).graphs(batch, getattr(data, "num_graphs", None))
+    G = seg.G
+    ei = edge_index.contiguous()
+    ws_bytes = max(call_size("gsat_subgraph_workspace_bytes", N, E), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    edge_mask = torch.empty(E, dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    new_ptr = torch.empty(G + 1, dtype=torch.int32, device=dev)
+
+    def run(phases, n_out, e_out, out):
+        call("gsat_subgraph_index", ptr(ei) if E else None, E, N, ptr(seg.batch) if N else None, ptr(seg.node_ptr), G,
+             ptr(keep) if keep.numel() else None, mode, int(bool(drop_isolated)), phases, n_out, e_out, 1,
+             *(ptr(t) if t is not None and t.numel() else None for t in out), ptr(new_ptr), ptr(edge_mask) if E else None,
+             ptr(counts), ptr(ws), ws_bytes, stream())
+
+    if sizes is None:
+        run(1, -1, -1, (None, None, None, None))
+        n_out, e_out, _, bad = counts.tolist()               # the one host read
+        if bad:
+            raise ValueError("edge_index contains node ids outside [0, num_nodes)")
+    else:
+        n_out, e_out = sizes
+    node_id = torch.empty(n_out, dtype=torch.int64, device=dev)
+    edge_id = torch.empty(e_out, dtype=torch.int64, device=dev)
+    new_ei = torch.empty(2, e_out, dtype=torch.int64, device=dev)
+    new_batch = torch.empty(n_out, dtype=torch.int64, device=dev)
+    run(2 if sizes is None else 3, n_out, e_out, (node_id, edge_id, new_ei, new_batch))
+
+    sub = SubgraphBatch(x=gather_rows(x, node_id), edge_index=new_ei, batch=new_batch, y=getattr(data, "y", None), num_graphs=G,
+                        node_id=node_id, edge_id=edge_id, edge_mask=edge_mask.view(torch.bool), node_ptr=new_ptr, counts=counts,
+                        sizes=(n_out, e_out))
+    for name, index in (("edge_attr", edge_id), ("edge_label", edge_id), ("node_label", node_id)):
+        t = getattr(data, name, None)
+        if isinstance(t, torch.Tensor):
+            _need_cuda(t)
+            if int(t.shape[0]) != (E if index is edge_id else N):
+                raise ValueError(f"{name} has {t.shape[0]} rows")
+            t = gather_rows(t, index)
+        setattr(sub, name, t)
+    if not capturing:
+        sub.prime()
+    return sub
+
+
+def edge_subgraph(data, edge_keep: torch.Tensor, drop_isolated: bool = True, sizes: Optional[Tuple[int, int]] = None) -> SubgraphBatch:
+    """The batch restricted to the edges with ``edge_keep`` (bool / nonzero, [E]).  ``drop_isolated``: keep only the endpoints of the
+    kept edges (relabelled); otherwise every node stays and only ``edge_index`` and the edge attributes shrink.
+    ``data``: anything with ``x``, ``edge_index``, ``batch`` and optionally ``edge_attr``, ``edge_label``, ``node_label``, ``y``,
+    ``num_graphs`` (a synth.Batch, a PyG batch).  One host read (the result's sizes) per call; ``sizes=(N', E')`` skips it -- the call
+    is then capturable (bool / uint8 masks), nothing is written beyond the declared sizes and a wrong declaration raises at the
+    result's ``.check()``."""
+    if not isinstance(edge_keep, torch.Tensor):
+        raise ValueError("edge_keep must be a tensor")
+    return _extract(data, edge_keep, 0, drop_isolated, sizes)
+
+
+def node_subgraph(data, node_keep: torch.Tensor, sizes: Optional[Tuple[int, int]] = None) -> SubgraphBatch:
+    """PyG ``subgraph(node_keep, edge_index, relabel_nodes=True)`` on a whole collated batch (example/trainer.py:168): the kept nodes,
+    relabelled in order, and the edges with both endpoints kept.  ``node_keep``: a bool mask [N]; an int64 id list is turned into
+    one."""
+    if not isinstance(node_keep, torch.Tensor):
+        raise ValueError("node_keep must be a tensor")
+    if node_keep.dtype == torch.int64:
+        _need_cuda(data.x, node_keep)
+        mask = torch.zeros(int(data.x.shape[0]), dtype=torch.uint8, device=node_keep.device)
+        mask[node_keep.reshape(-1)] = 1
+        node_keep = mask
+    return _extract(data, node_keep, 1, False, sizes)
+
+
+def explanation_subgraph(att, data, k: Optional[int] = None, ratio: Optional[float] = None, complement: bool = False,
+                         drop_isolated: bool = True, path: str = "auto") -> SubgraphBatch:
+    """Every graph's ``k`` (or ``ceil(ratio * E_g)``) highest-attention edges as a batch of their own (``complement``: everything
+    BUT those edges); ties as in :mod:`dp_gsat_amd.explain` (lower edge id first).  The kept edges' attention rides along as
+    ``edge_att = att[edge_id]``."""
+    if (k is None) == (ratio is None):
+        raise ValueError("give exactly one of k and ratio")
+    a = ops.edge_tensor(att)
+    if not isinstance(a, torch.Tensor) or a.numel() != int(data.edge_index.shape[1]):
+        raise ValueError(f"attention must have one entry for each of the {int(data.edge_index.shape[1])} edges")
+    _need_cuda(a, data.edge_index, data.batch, data.x)
+    mask = topk_edge_mask(a, data.edge_index, data.batch, k=k, ratio=ratio, num_graphs=getattr(data, "num_graphs", None), path=path)
+    if complement:
+        mask = ~mask
+    sub = edge_subgraph(data, mask, drop_isolated=drop_isolated)
+    sub.edge_att = gather_rows(a.detach(), sub.edge_id)
+    return sub
+
+
+def explanation_fidelity(clf, data, att, k: Optional[int] = None, ratio: Optional[float] = None, drop_isolated: bool = False) -> dict:
+    """Fidelity of the top-k explanation for the backbone ``clf``: three forwards WITHOUT ``edge_atten`` (eval mode, no grad) -- the
+    full batch, the explanation alone, the batch with the explanation removed -- on compacted graphs, which is what makes the
+    numbers right for PNA.  Returns device tensors: ``logits_full / logits_keep / logits_drop [G, C]`` and the scalars
+    ``fidelity_plus = mean_g(p_full - p_drop)``, ``fidelity_minus = mean_g(p_full - p_keep)`` with ``p`` the probability of the class
+    the full model predicts (one logit: sigmoid and its sign; otherwise softmax and argmax).  The results stay on the device; the
+    two extractions read their sizes back once each."""
+    was_training = clf.training
+    clf.eval()
+    try:
+        with torch.no_grad():
+            keep = explanation_subgraph(att, data, k=k, ratio=ratio, complement=False, drop_isolated=drop_isolated)
+            drop = explanation_subgraph(att, data, k=k, ratio=ratio, complement=True, drop_isolated=drop_isolated)
+            for sub in (keep, drop):
+                if sub.num_nodes == 0:
+                    raise ValueError("an extraction kept no node at all: use drop_isolated=False")
+            for sub in (keep, drop):           # also for an extraction without edges: the forwards below must return num_graphs rows
+                get_index(sub.edge_index, sub.num_nodes).graphs(sub.batch, sub.num_graphs)
+            full, lk, ld = (clf(d.x, d.edge_index, d.batch, getattr(d, "edge_attr", None)) for d in (data, keep, drop))
+            if full.dim() == 2 and full.shape[1] > 1:
+                cls = full.argmax(dim=1, keepdim=True)
+                p_full, p_keep, p_drop = (torch.softmax(z, dim=1).gather(1, cls).view(-1) for z in (full, lk, ld))
+            else:
+                sign = torch.where(full >= 0, 1.0, -1.0)
+                p_full, p_keep, p_drop = (torch.sigmoid(sign * z).view(-1) for z in (full, lk, ld))
+    finally:
+        clf.train(was_training)
+    return {"logits_full": full, "logits_keep": lk, "logits_drop": ld,
+            "fidelity_plus": (p_full - p_drop).mean(), "fidelity_minus": (p_full - p_keep).mean()}

@@ -651,6 +651,53 @@ size_t gsat_delta_kl_workspace_bytes(int64_t num_edges);
 int gsat_delta_kl(const float* att, const uint8_t* label, int64_t num_edges, double eps, float* out, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ================================== explanation subgraphs =================================== */
+
+/*
+ * Order-preserving extraction of a subgraph of a collated batch, with node relabelling.  replaces: the host-side
+ * subgraph(node_subset.cpu(), data.edge_index.cpu(), ...) of example/trainer.py:140-170.
+ * Inputs: edge_index int64[2,E]; N nodes; batch int64[N] (nullable: then no new_batch); node_ptr int32[G+1] (nullable: then no
+ * new_node_ptr); keep uint8 (nonzero = keep) and mode:
+ *   mode 0 (edge mode): keep has E entries.  drop_isolated != 0: the kept nodes are the endpoints of the kept edges;
+ *                       drop_isolated == 0: every node is kept.
+ *   mode 1 (node mode): keep has N entries; an edge is kept iff both endpoints are kept (PyG subgraph(..., relabel_nodes=True)).
+ * Kept items stay in their original relative order, so every output is unique:
+ *   node_id int64[cap_nodes]          old ids of the kept nodes, ascending
+ *   edge_id int64[cap_edges]          old ids of the kept edges, ascending
+ *   new_edge_index int64[2,cap_edges] endpoints relabelled by the rank of the node among the kept nodes (row stride cap_edges)
+ *   new_batch int64[cap_nodes]        batch[node_id]
+ *   new_node_ptr int32[G+1]           the exclusive scan of the kept nodes read at the old node_ptr: a graph that lost every node
+ *                                     becomes an empty segment, G does not change
+ *   edge_mask uint8[E]                required when E > 0: 0 / 1 per old edge, 1 iff the edge is kept (edge mode: the normalised
+ *                                     input); also the flag array the output phase reads
+ *   counts int64[4]                   (N', E', overflow flag, bad-id flag)
+ * Capacities (<= N / E): nothing is ever written at or beyond cap_nodes / cap_edges entries; entries between a smaller true count and
+ * the capacity are filled with id 0 (valid ids, never uninitialised memory, for the gathers that follow).  exact != 0: the overflow flag is set when
+ * N' != cap_nodes or E' != cap_edges; exact == 0: when N' > cap_nodes or E' > cap_edges.  An edge with a node id outside [0, N) sets the
+ * bad-id flag, is dropped (edge_mask 0) and its ids are never dereferenced.
+ * phases: 1 = count only (flags, edge_mask and counts; capacities may be -1 = not declared), 2 = outputs only, from the flags a
+ * phase-1 call left in the SAME workspace and edge_mask, 3 = both.  A caller that reads counts between 1 and 2 can size its outputs
+ * exactly; a caller that knows the sizes passes 3 with exact = 1 and never reads anything back (capturable).
+ * Launches: 4 (6 in edge mode with drop_isolated: the endpoint marks need a cleared array and a pass of their own), independent of
+ * G, N, E; kernels only, no memset / memcpy nodes.  Two-level scan over workgroups of gsat_subgraph_block_items() items, no
+ * inter-workgroup waiting; the endpoint marks are byte stores of 1 that race only with identical values.  N, E, G < 2^31
+ * (GSAT_ERR_UNSUPPORTED otherwise).  workspace: gsat_subgraph_workspace_bytes(N, E).
+ */
+int64_t gsat_subgraph_block_items(void);
+size_t gsat_subgraph_workspace_bytes(int64_t num_nodes, int64_t num_edges);
+int gsat_subgraph_index(const int64_t* edge_index, int64_t num_edges, int64_t num_nodes, const int64_t* batch, const int32_t* node_ptr,
+                        int64_t num_graphs, const uint8_t* keep, int mode, int drop_isolated, int phases, int64_t cap_nodes,
+                        int64_t cap_edges, int exact, int64_t* node_id, int64_t* edge_id, int64_t* new_edge_index, int64_t* new_batch,
+                        int32_t* new_node_ptr, uint8_t* edge_mask, int64_t* counts, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/*
+ * out[i,:] = table[index[i],:] for n rows of row_bytes >= 1 bytes each, any dtype (both row-major, contiguous).  16-byte lanes when
+ * row_bytes, table and out are all 16-byte aligned, otherwise 8-, 4- or 1-byte lanes from the actual alignment.  The indices are
+ * trusted (they come from gsat_subgraph_index).
+ */
+int gsat_gather_rows(const void* table, const int64_t* index, int64_t n, int64_t row_bytes, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
