@@ -18,10 +18,14 @@ from .graph_index import BatchIndex, clear_cache, get_index, set_strict, set_syn
 from .utils import process_data, reorder_like, set_seed
 from .explain import EdgeRanking, ExplanationMeter, attention_auroc, delta_kl, precision_at_k, rank_edges, topk_edge_mask
 from .subgraph import SubgraphBatch, edge_subgraph, explanation_fidelity, explanation_subgraph, gather_rows, node_subgraph
+from .evaluate import (AttentionHistogram, EvaluationMeter, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve,
+                       task_auroc_counts)
 
 __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "get_preds", "GINConv", "GINEConv",
            "PNAConvSimple", "GIN", "PNA", "GSAT", "ExtractorMLP", "concrete_sample", "get_r", "gumbel_sigmoid",
            "info_loss", "lift_node_att_to_edge_att", "symmetrise_edge_att", "BatchIndex", "get_index", "clear_cache", "set_sync_free", "set_strict",
            "process_data", "reorder_like", "set_seed", "DualGSAT", "f1_sparsity_loss", "LEConv", "SPMotifNet", "PackedDataset", "line_graph", "line_graph_undirected",
            "EdgeRanking", "ExplanationMeter", "attention_auroc", "delta_kl", "precision_at_k", "rank_edges", "topk_edge_mask",
-           "SubgraphBatch", "edge_subgraph", "node_subgraph", "explanation_subgraph", "explanation_fidelity", "gather_rows"]
+           "SubgraphBatch", "edge_subgraph", "node_subgraph", "explanation_subgraph", "explanation_fidelity", "gather_rows",
+           "AttentionHistogram", "EvaluationMeter", "attention_histogram", "classifier_accuracy", "classifier_rocauc", "pr_curve",
+           "task_auroc_counts"]

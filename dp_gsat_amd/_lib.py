@@ -101,6 +101,9 @@ SIGNATURES = {
     "gsat_auroc": (INT, [P, P, I64, P, P, SZ, P]),
     "gsat_delta_kl_workspace_bytes": (SZ, [I64]),
     "gsat_delta_kl": (INT, [P, P, I64, F64, P, P, SZ, P]),
+    "gsat_auroc_tasks_workspace_bytes": (SZ, [I64, I64]),
+    "gsat_auroc_tasks": (INT, [P, P, I64, I64, P, P, SZ, P]),
+    "gsat_att_histogram": (INT, [P, P, I64, I64, F64, F64, P, P, P]),
     "gsat_subgraph_block_items": (I64, []),
     "gsat_subgraph_workspace_bytes": (SZ, [I64, I64]),
     "gsat_subgraph_index": (INT, [P, I64, I64, P, P, I64, P, INT, INT, INT, I64, I64, INT, P, P, P, P, P, P, P, P, SZ, P]),

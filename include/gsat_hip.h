@@ -651,6 +651,38 @@ size_t gsat_delta_kl_workspace_bytes(int64_t num_edges);
 int gsat_delta_kl(const float* att, const uint8_t* label, int64_t num_edges, double eps, float* out, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ==================================== evaluation scores ===================================== */
+
+/*
+ * Exact, tie-aware ROC-AUC of every column (task) of score fp32[R,T] against label fp32[R,T], both row-major.  Labels: NaN
+ * (label != label) = unlabelled, skipped; 0 = negative; anything else = positive.  out uint64[T,3] = (U2, P, Nn) per task with
+ * exactly the meaning gsat_auroc gives them, over the labelled rows of that task; a task without a labelled row gets (0, 0, 0).
+ * Integers only: bitwise repeatable.  -0.0 == +0.0; NaN scores are unsupported (their position is unspecified; memory-safe).
+ * One stable radix sort of (task | score bits) keys over 32 + bits(T) bits with the unlabelled entries under a sentinel task, one
+ * scan of the negatives, the tasks' segment bounds and one integer pass (64-bit integer atomics: order independent).  Kernels only,
+ * capturable; workspace gsat_auroc_tasks_workspace_bytes(R, T).  Any R, T >= 0 with R * T < 2^31 (GSAT_ERR_UNSUPPORTED otherwise).
+ * replaces: the ogb Evaluator's rocauc on host copies (src/run_gsat.py:756-759, src/pretrain_clf.py:104), which is the mean of
+ * U2 / (2 P Nn) over the tasks with P > 0 and Nn > 0.
+ */
+size_t gsat_auroc_tasks_workspace_bytes(int64_t num_rows, int64_t num_tasks);
+int gsat_auroc_tasks(const float* score, const float* label, int64_t num_rows, int64_t num_tasks, uint64_t* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/*
+ * Two-class histogram of att fp32[E]: hist uint64[2,bins] (row 0 = label 0 / background, row 1 = label nonzero / signal) and
+ * outside uint64[2] are ADDED TO, never overwritten: the caller zeroes them once and accumulates batch after batch.
+ * label uint8[E], nullable: then every entry is class 0.  1 <= bins <= 4096, lo < hi (GSAT_ERR_ARG otherwise).
+ * The bin is part of the contract (fp64, no contraction): t = ((double)a - lo) * ((double)bins / (hi - lo)),
+ * bin = min((int)floor(t), bins - 1) -- a == hi lands in the closed last bin, like numpy's; a < lo, a > hi or NaN is not binned
+ * and adds 1 to outside[class].  -0.0 is 0.
+ * Per-workgroup uint32 counters in LDS (<= 32 KiB), lanes of a wavefront with equal counters combined before the LDS atomic, non-zero
+ * counters flushed with 64-bit global integer atomics: no float atomics, the result does not depend on any order.  One launch, no
+ * workspace, capturable.  E < 2^40 (GSAT_ERR_UNSUPPORTED otherwise).
+ * replaces: the host arrays behind add_histogram(bkg / signal_att_weights) and add_pr_curve (src/run_gsat.py:764-776).
+ */
+int gsat_att_histogram(const float* att, const uint8_t* label, int64_t num_edges, int64_t bins, double lo, double hi, uint64_t* hist,
+                       uint64_t* outside, void* stream);
+
 /* ================================== explanation subgraphs =================================== */
 
 /*
