@@ -66,6 +66,7 @@ SIGNATURES = {
     "gsat_embsum_fwd": (INT, [P, P, INT, P, I64, I64, P, P]),
     "gsat_onehot_rows": (INT, [P, P, INT, I64, I64, P, P]),
     "gsat_gemm_workspace_floats": (SZ, [INT, I64, I64, I64]),
+    "gsat_gemm_plan": (INT, [INT, INT, INT, I64, I64, I64, INT, INT, I64, P]),
     "gsat_gemm_f32": (INT, [INT, INT, I64, I64, I64, P, I64, P, I64, P, I64, P, INT, P, SZ, P]),
     "gsat_gemm_bf16x3": (INT, [INT, INT, I64, I64, I64, P, I64, P, I64, P, I64, P, INT, P, SZ, P]),
     "gsat_attn_fwd_workspace_bytes": (SZ, [P]),

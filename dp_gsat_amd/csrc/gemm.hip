@@ -184,9 +184,10 @@ __global__ __launch_bounds__(GT) void k_gemm_f32(const float* __restrict__ A, in
 
 // ================================================================================================================
 // Split-bf16 ("bf16x3") variant for large products: x = hi + lo with hi = bf16(x), lo = bf16(x - hi); the product is
-// accumulated in fp32 as hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate per instruction, so
-// ~5x per product at three instructions).  The dropped lo*lo term and the rounding of lo are ~2^-17 relative to |a||b|,
-// i.e. the result stays inside the 1e-4 parity band with two orders of magnitude to spare (tests/test_gpu_gemm.py).
+// accumulated in fp32 as lo*lo + lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate per instruction, so
+// ~4x per product at four instructions).  bf16 keeps 8 significand bits: |lo| <= 2^-8 |x| and hi + lo represents x to 2^-17, so
+// the four products leave (1 + 2^-17)^2 - 1 ~ 2^-16 of |a||b| per term whatever the data.  Without lo*lo (itself up to 2^-16) the
+// worst case is 2^-15, which a K = 4 product reached (tests/test_gpu_gemm_paths.py bounds every element by 2^-16 + 2 K 2^-24).
 // LDS holds four bf16 planes (A_hi, A_lo, B_hi, B_lo) in [row][k] order with 80-byte rows (64 B of k + 16 B pad: the
 // ds_read_b128 operand fetches of a 16-lane group then hit 16 distinct 16-byte bank slots).
 // ================================================================================================================
@@ -401,6 +402,7 @@ __global__ __launch_bounds__(GT, (VIRT == 1 && TM == 2 && TN == 2) ? 3 : 1) void
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bl[j], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
@@ -576,13 +578,13 @@ __global__ __launch_bounds__(WS_THREADS, (KR <= 64 && NQ <= 4) ? 4 : 2) void k_g
 }
 
 // ================================================================================================================
-// The same weight-stationary scheme on the split-bf16 path (hi*hi + hi*lo + lo*hi, 32x32x16 bf16 MFMA) for the BACKWARD-data products of
+// The same weight-stationary scheme on the split-bf16 path (lo*lo + lo*hi + hi*lo + hi*hi, 32x32x16 bf16 MFMA) for the BACKWARD-data products of
 // the extractor (da1 = dh2 W2, demb = dh1 W1: 51 639 x 256 x 128 and 51 639 x 128 x 256 at C3).  On the 128 x 128 tile kernel these run
 // 28-30 us against a ~16 us floor for their 79 MB of operands: four K-slabs per tile, a prologue and an epilogue per tile.  Here a
 // persistent workgroup keeps its share of B as bf16 hi / lo fragments in registers (wave w: column block w % NB, k-split w / NB; KSTEPS
 // 16-deep steps = 8 KSTEPS registers) and streams 32-row tiles of A: the staging threads split each fp32 value ONCE into the two bf16
 // planes of a double-buffered LDS image, every wave then reads its operand fragments with one ds_read_b128 per plane and step.  The MFMA
-// time is a quarter of the fp32 kernel's, so the launch is bound by its HBM traffic.  k-splits meet in LDS in fixed order.
+// time is a third of the fp32 kernel's, so the launch is bound by its HBM traffic.  k-splits meet in LDS in fixed order.
 // ================================================================================================================
 template <bool B_T, int KSTEPS, int NQ>
 __global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
@@ -662,6 +664,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __res
         for (int s_ = 0; s_ < KSTEPS; ++s_) {
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(arow + 32 * s_);
             const bf16x8 al = *reinterpret_cast<const bf16x8*>(arow + PLANE + 32 * s_);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bl[s_], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s_], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s_], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s_], acc, 0, 0, 0);
@@ -862,9 +865,7 @@ static int ws_launch(hipStream_t stream, dim3 grid, size_t lds, const float* A, 
     return GSAT_OK;
 }
 static int gemm_ws(hipStream_t stream, bool b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
-                   float* C, int64_t ldc, const float* bias) {
-    int nb = 0, kr = 0;
-    GSAT_REQUIRE(ws_geometry(N, K, &nb, &kr), GSAT_ERR_UNSUPPORTED, "gemm_ws: unsupported shape");
+                   float* C, int64_t ldc, const float* bias, int nb, int kr) {
     GSAT_REQUIRE(lda % 4 == 0 && ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && (!b_t || ldb % 4 == 0), GSAT_ERR_ARG, "gemm_ws: alignment");
     const int tiles = (int)ceil_div(M, WS_ROWS);
     const int chunks = (int)ceil_div(N, 256);
@@ -916,9 +917,7 @@ static int wsx3_launch(hipStream_t stream, dim3 grid, size_t lds, const float* A
     return GSAT_OK;
 }
 static int gemm_wsx3(hipStream_t stream, bool b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
-                     float* C, int64_t ldc, bool accumulate) {
-    int nb = 0, st = 0;
-    GSAT_REQUIRE(wsx3_geometry(N, K, &nb, &st), GSAT_ERR_UNSUPPORTED, "gemm_wsx3: unsupported shape");
+                     float* C, int64_t ldc, bool accumulate, int nb, int st) {
     const int tiles = (int)ceil_div(M, WS_ROWS);
     const size_t lds = (size_t)4 * WS_ROWS * (2 * K + 16);
     const int nq = (int)(K / 64);
@@ -938,21 +937,34 @@ static int gemm_wsx3(hipStream_t stream, bool b_t, int64_t M, int64_t N, int64_t
     GSAT_REQUIRE(false, GSAT_ERR_UNSUPPORTED, "gemm_wsx3: K = %lld is not 64, 128, 256 or 512", (long long)K);
 }
 
-// C[M,N] (+)= op(A) op(B) (+ bias).  a_t: A given as [K,M]; b_t: B given as [N,K].  K % 4 == 0 and the
-// contiguous extents must be multiples of 4 (float4 staging).  `ws` is needed when gemm_splits() > 1.
-int gemm_f32(hipStream_t stream, bool a_t, bool b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
-             int64_t ldb, float* C, int64_t ldc, const float* bias, bool accumulate, float* ws, size_t ws_floats, bool allow_split, SlabJob* defer) {
-    if (defer) defer->nslab = 0;
-    if (M <= 0 || N <= 0) return GSAT_OK;
-    xcd_switch_once();
-    GSAT_REQUIRE(K > 0 && A && B && C, GSAT_ERR_ARG, "gemm_f32: bad argument");
-    GSAT_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && (a_t ? M % 4 == 0 : K % 4 == 0) && (b_t ? K % 4 == 0 : N % 4 == 0), GSAT_ERR_UNSUPPORTED,
-                 "gemm_f32: contiguous extents and leading dimensions must be multiples of 4 (M=%lld N=%lld K=%lld)", (long long)M, (long long)N, (long long)K);
-    GSAT_REQUIRE(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0) && ldc % 4 == 0 && (!bias || (uintptr_t)bias % 16 == 0),
-                 GSAT_ERR_ARG, "gemm_f32: operands, output and bias must be 16-byte aligned with ldc % 4 == 0");
+// Every dispatch decision of gemm_f32() for one product: which kernel family runs, with which template parameters, how many K splits and
+// which slab sum.  gemm_f32() launches exactly what this returns and gsat_gemm_plan() reports it, so the two cannot drift apart.  Host
+// arithmetic and environment reads only: no launch, no HIP call.
+enum { GEMM_TILE_F32 = 0, GEMM_TILE_X3 = 1, GEMM_WS_F32 = 2, GEMM_WS_X3 = 3 };
+struct GemmPlan {
+    int family;          // GEMM_*
+    int tm, tn;          // tile kernels: (64 tm) x (64 tn) block tile; 0 for the weight-stationary kernels
+    int splits;          // K splits (blockIdx.z), 1 = none
+    int reduce;          // slab sum of a split product: 0 none, 1 scalar k_slab_reduce, 4 | 8 | 16 = lanes per float4 of k_slab_reduce4
+    int nb, kr, nq;      // weight-stationary kernels: column blocks per workgroup, KR (fp32) | KSTEPS (split-bf16), NQ; else 0
+};
+static GemmPlan gemm_plan(bool allow_split, bool a_t, bool b_t, int64_t M, int64_t N, int64_t K, bool has_bias, bool accumulate, int64_t ldb) {
+    GemmPlan p{};
     const bool split = use_bf16x3(M, N, K, allow_split);
-    if (!a_t && !split && !accumulate && ws_applicable(M, N, K)) return gemm_ws(stream, b_t, M, N, K, A, lda, B, ldb, C, ldc, bias);
-    if (!a_t && split && !bias && wsx3_applicable(M, N, K) && (b_t ? ldb % 4 == 0 : true)) return gemm_wsx3(stream, b_t, M, N, K, A, lda, B, ldb, C, ldc, accumulate);
+    p.splits = 1;
+    if (!a_t && !split && !accumulate && ws_applicable(M, N, K)) {
+        p.family = GEMM_WS_F32;
+        ws_geometry(N, K, &p.nb, &p.kr);
+        p.nq = (int)(K / 64);
+        return p;
+    }
+    if (!a_t && split && !has_bias && wsx3_applicable(M, N, K) && (b_t ? ldb % 4 == 0 : true)) {
+        p.family = GEMM_WS_X3;
+        wsx3_geometry(N, K, &p.nb, &p.kr);
+        p.nq = (int)(K / 64);
+        return p;
+    }
+    p.family = split ? GEMM_TILE_X3 : GEMM_TILE_F32;
     const int splits = gemm_splits(M, N, K, a_t);
     int tm = 2, tn = 2;
     if (splits == 1) gemm_tile(M, N, K, &tm, &tn);
@@ -965,6 +977,29 @@ int gemm_f32(hipStream_t stream, bool a_t, bool b_t, int64_t M, int64_t N, int64
     // split-bf16: the per-tile staging (fp32 -> hi/lo, LDS planes) is what costs, so the largest tile wins even when it leaves
     // fewer workgroups than CUs x occupancy (51 639 x 128 x 1024: 57 us at 128x128 against 69 us at 128x64)
     if (split && splits == 1 && !getenv("GSAT_GEMM_TILE")) { tm = 2; tn = N > 64 ? 2 : 1; }
+    p.tm = tm; p.tn = tn; p.splits = splits;
+    // the 16-byte slab sums need N % 4 == 0 (the slabs are [M, N] dense); gemm_f32 falls back to the scalar sum for a misaligned workspace
+    if (splits > 1) p.reduce = N % 4 != 0 ? 1 : (splits >= 128 ? 16 : (splits >= 64 ? 8 : 4));
+    return p;
+}
+
+// C[M,N] (+)= op(A) op(B) (+ bias).  a_t: A given as [K,M]; b_t: B given as [N,K].  K % 4 == 0 and the
+// contiguous extents must be multiples of 4 (float4 staging).  `ws` is needed when gemm_splits() > 1.
+int gemm_f32(hipStream_t stream, bool a_t, bool b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+             int64_t ldb, float* C, int64_t ldc, const float* bias, bool accumulate, float* ws, size_t ws_floats, bool allow_split, SlabJob* defer) {
+    if (defer) defer->nslab = 0;
+    if (M <= 0 || N <= 0) return GSAT_OK;
+    xcd_switch_once();
+    GSAT_REQUIRE(K > 0 && A && B && C, GSAT_ERR_ARG, "gemm_f32: bad argument");
+    GSAT_REQUIRE(lda % 4 == 0 && ldb % 4 == 0 && (a_t ? M % 4 == 0 : K % 4 == 0) && (b_t ? K % 4 == 0 : N % 4 == 0), GSAT_ERR_UNSUPPORTED,
+                 "gemm_f32: contiguous extents and leading dimensions must be multiples of 4 (M=%lld N=%lld K=%lld)", (long long)M, (long long)N, (long long)K);
+    GSAT_REQUIRE(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0) && ldc % 4 == 0 && (!bias || (uintptr_t)bias % 16 == 0),
+                 GSAT_ERR_ARG, "gemm_f32: operands, output and bias must be 16-byte aligned with ldc % 4 == 0");
+    const GemmPlan plan = gemm_plan(allow_split, a_t, b_t, M, N, K, bias != nullptr, accumulate, ldb);
+    if (plan.family == GEMM_WS_F32) return gemm_ws(stream, b_t, M, N, K, A, lda, B, ldb, C, ldc, bias, plan.nb, plan.kr);
+    if (plan.family == GEMM_WS_X3) return gemm_wsx3(stream, b_t, M, N, K, A, lda, B, ldb, C, ldc, accumulate, plan.nb, plan.kr);
+    const bool split = plan.family == GEMM_TILE_X3;
+    const int splits = plan.splits, tm = plan.tm, tn = plan.tn;
     dim3 grid((unsigned)ceil_div(N, 64 * tn), (unsigned)ceil_div(M, 64 * tm), (unsigned)splits);
     int kps = (int)(ceil_div(ceil_div(K, splits), GK) * GK);
     float* out = C;
@@ -996,13 +1031,15 @@ int gemm_f32(hipStream_t stream, bool a_t, bool b_t, int64_t M, int64_t N, int64
 #undef LAUNCH
     GSAT_LAUNCH_CHECK();
     if (splits > 1) {
-        const bool vec = N % 4 == 0 && ldc % 4 == 0 && slab % 4 == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)ws & 15) == 0;
+        // the plan's 16-byte sum needs 16-byte aligned rows in the output and in the workspace, else the scalar sum
+        const bool vec = plan.reduce != 1 && ldc % 4 == 0 && slab % 4 == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)ws & 15) == 0;
+        const int reduce = vec ? plan.reduce : 1;
         if (defer && vec) { *defer = SlabJob{ws, splits, slab, (int)M, (int)N, ldc, accumulate ? 1 : 0, C}; return GSAT_OK; }
-        if (vec && splits >= 128)
+        if (reduce == 16)
             k_slab_reduce4<16><<<(unsigned)ceil_div(M * N * 4, 256), 256, 0, stream>>>(ws, splits, slab, (int)M, (int)N, ldc, accumulate ? 1 : 0, C);
-        else if (vec && splits >= 64)
+        else if (reduce == 8)
             k_slab_reduce4<8><<<(unsigned)ceil_div(M * N * 2, 256), 256, 0, stream>>>(ws, splits, slab, (int)M, (int)N, ldc, accumulate ? 1 : 0, C);
-        else if (vec)
+        else if (reduce == 4)
             k_slab_reduce4<4><<<(unsigned)ceil_div(M * N, 256), 256, 0, stream>>>(ws, splits, slab, (int)M, (int)N, ldc, accumulate ? 1 : 0, C);
         else
             k_slab_reduce<<<(unsigned)ceil_div(M * N, 256), 256, 0, stream>>>(ws, splits, slab, (int)M, (int)N, ldc, accumulate ? 1 : 0, C);
@@ -1119,12 +1156,24 @@ int gsat_gemm_f32(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const float
     return gemm_f32((hipStream_t)stream, a_t != 0, b_t != 0, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate != 0, workspace, workspace_floats, false);
 }
 
-/* same product on the split-bf16 (hi*hi + hi*lo + lo*hi) MFMA path when it is large enough to pay; see include/gsat_hip.h */
+/* same product on the split-bf16 (lo*lo + lo*hi + hi*lo + hi*hi) MFMA path when it is large enough to pay; see include/gsat_hip.h */
 int gsat_gemm_bf16x3(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                      float* C, int64_t ldc, const float* bias, int accumulate, float* workspace, size_t workspace_floats, void* stream) {
     return gemm_f32((hipStream_t)stream, a_t != 0, b_t != 0, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate != 0, workspace, workspace_floats, true);
 }
 
 size_t gsat_gemm_workspace_floats(int a_t, int64_t M, int64_t N, int64_t K) { return gemm_workspace_floats(M, N, K, a_t != 0); }
+
+/* the dispatch decisions of gsat_gemm_f32 (allow_split == 0) / gsat_gemm_bf16x3 for these arguments; see include/gsat_hip.h */
+int gsat_gemm_plan(int allow_split, int a_t, int b_t, int64_t M, int64_t N, int64_t K, int has_bias, int accumulate, int64_t ldb, int32_t* plan) {
+    GSAT_REQUIRE(plan && M > 0 && N > 0 && K > 0, GSAT_ERR_ARG, "gsat_gemm_plan: bad argument");
+    GSAT_REQUIRE(ldb % 4 == 0 && (a_t ? M % 4 == 0 : K % 4 == 0) && (b_t ? K % 4 == 0 : N % 4 == 0), GSAT_ERR_UNSUPPORTED,
+                 "gsat_gemm_plan: contiguous extents and leading dimensions must be multiples of 4 (M=%lld N=%lld K=%lld)", (long long)M, (long long)N, (long long)K);
+    const GemmPlan p = gemm_plan(allow_split != 0, a_t != 0, b_t != 0, M, N, K, has_bias != 0, accumulate != 0, ldb);
+    GSAT_REQUIRE(!(has_bias && p.splits > 1), GSAT_ERR_UNSUPPORTED, "gsat_gemm_plan: bias with split-K");
+    const int32_t v[8] = {p.family, p.tm, p.tn, p.splits, p.reduce, p.nb, p.kr, p.nq};
+    memcpy(plan, v, sizeof(v));
+    return GSAT_OK;
+}
 
 }  // extern "C"

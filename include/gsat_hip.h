@@ -392,12 +392,24 @@ int gsat_onehot_rows(const int64_t* x, const int32_t* dims, int ncol, int64_t N,
  * gsat_gemm_workspace_floats() is only needed when a_t != 0; bias (nullable, [N]) only when a_t == 0.
  */
 size_t gsat_gemm_workspace_floats(int a_t, int64_t M, int64_t N, int64_t K);
+/* what gsat_gemm_f32 (allow_split == 0) or gsat_gemm_bf16x3 (allow_split != 0) will launch for these arguments (host-side, no launch, no
+   HIP call; the dispatcher itself runs on the same function).  plan is HOST int32[8]:
+     [0] kernel family: 0 = tile fp32, 1 = tile split-bf16, 2 = weight-stationary fp32, 3 = weight-stationary split-bf16
+     [1] TM, [2] TN: the block tile is (64 TM) x (64 TN); 0 for the weight-stationary kernels
+     [3] K splits (1 = none; > 1 needs the workspace)
+     [4] ordered slab sum of a split product: 0 = none, 1 = scalar, 4 | 8 | 16 = lanes per 16-byte output quad (the dispatcher takes the
+         scalar sum instead when the workspace is not 16-byte aligned)
+     [5] NB, [6] KR (fp32) or KSTEPS (split-bf16), [7] NQ of the weight-stationary kernels; 0 for the tile kernels
+   The environment's tuning overrides (GSAT_GEMM_TILE, GSAT_GEMM_PRECISION, ...) apply as in the dispatcher.  For tests and logs. */
+int gsat_gemm_plan(int allow_split, int a_t, int b_t, int64_t M, int64_t N, int64_t K, int has_bias, int accumulate,
+                   int64_t ldb, int32_t* plan);
 int gsat_gemm_f32(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                   const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int accumulate,
                   float* workspace, size_t workspace_floats, void* stream);
 /*
  * Same contract, but products of >= 2 GFLOP run as split-bf16: every fp32 operand x = hi + lo (two bf16), the product is
- * hi*hi + hi*lo + lo*hi accumulated in fp32 on v_mfma_f32_32x32x16_bf16 (relative error ~1e-5 of |A||B|, 2-5x faster).
+ * lo*lo + lo*hi + hi*lo + hi*hi accumulated in fp32 on v_mfma_f32_32x32x16_bf16 (componentwise error <= 2^-16 of |A||B| plus the fp32
+ * accumulation; 2-5x faster).
  * For callers whose outputs are not re-normalised by a small per-graph sigma (the backbone's Linear layers).
  */
 int gsat_gemm_bf16x3(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,

@@ -151,7 +151,7 @@ def test_gemm_weight_stationary(dev, b_t, M, N, K):
     (51639, 256, 128), (51639, 128, 256),      # C3 extractor backward: da1 = dh2 W2 (8 column blocks) ; demb = dh1 W1 (4 column blocks x 2 k-splits)
     (12801, 256, 64), (12801, 64, 256),        # H = 64 edge mode
     (9001, 128, 64), (9001, 64, 128),
-    (20000, 256, 512), (8193, 32, 256),        # 8 fragment steps of 16 k at K = 512 ; one column block, 8 k-splits
+    (20000, 256, 512), (8193, 32, 256),        # 32 fragment steps: NOT weight-stationary, the 128 x 128 tile kernel (gsat_gemm_plan) ; one column block, 8 k-splits
     (20001, 1024, 128), (9000, 512, 64),       # wide outputs: 256-column chunks (the backbone's dx = dy W at C3: 51 639 x 1024 x 128)
 ])
 def test_gemm_weight_stationary_split_bf16(dev, bf16x3, b_t, M, N, K):
