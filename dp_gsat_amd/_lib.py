@@ -55,6 +55,8 @@ SIGNATURES = {
     "gsat_bn_bwd": (INT, [P, P, P, P, P, P, I64, I64, INT, INT, P, P, P, P, P]),
     "gsat_bn_act_fwd": (INT, [P, P, P, P, P, I64, I64, INT, F32, F32, INT, P, F32, U64, P, P, P, P, P, P]),
     "gsat_bn_act_bwd": (INT, [P, P, P, P, P, P, I64, I64, INT, INT, F32, U64, P, P, P, P, P, P, P]),
+    "gsat_bn_act_fwd_valid": (INT, [P, P, P, P, P, I64, I64, INT, F32, F32, INT, P, F32, U64, P, P, P, P, P, P, P]),
+    "gsat_bn_act_bwd_valid": (INT, [P, P, P, P, P, P, I64, I64, INT, INT, F32, U64, P, P, P, P, P, P, P, P]),
     "gsat_bn_local_sum": (INT, [P, P, I64, I64, P, P, P]),
     "gsat_bn_apply_fwd": (INT, [P, P, P, P, P, I64, I64, INT, P, F32, U64, P, P, P]),
     "gsat_bn_local_bwd_sums": (INT, [P, P, P, P, P, P, I64, I64, INT, F32, U64, P, P, P, P, P]),
@@ -85,6 +87,9 @@ SIGNATURES = {
     "gsat_symmetrise": (INT, [P, P, P, I64, P, P]),
     "gsat_info_loss_fwd": (INT, [P, P, F32, I64, P, P, P]),
     "gsat_info_loss_bwd": (INT, [P, P, F32, P, I64, P, P]),
+    "gsat_info_loss_valid_fwd": (INT, [P, P, F32, P, I64, P, P, P, P]),
+    "gsat_info_loss_valid_bwd": (INT, [P, P, F32, P, P, I64, P, P, P]),
+    "gsat_collate_padded": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P, P]),
     "gsat_collate": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P]),
     "gsat_line_graph_pair_counts": (INT, [P, I64, P, P]),
     "gsat_line_graph": (INT, [P, P, P, I64, I64, P, P]),

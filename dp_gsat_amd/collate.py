@@ -15,6 +15,21 @@ from ._lib import call, ptr, stream
 from .synth import Batch
 
 
+class PaddedBatch(Batch):
+    """A batch of fixed capacity (``PackedDataset.collate_padded``): the ``B`` real graphs first, then one padding graph ``B`` that holds
+    the unused node rows and edge slots, so ``num_graphs = B + 1``.  Besides the fields of ``collate``'s batch it carries ``valid``
+    (int32[4] on the device: N_real, E_real, B, overflow), ``capacity = (N_cap, E_cap)``, ``node_src_row`` / ``edge_src_slot`` (the
+    dataset row / slot of every node / edge, -1 for padding) and optionally ``r`` (one device float: the info loss's r)."""
+
+
+def _take_padded(table, index):
+    """table[index] with zero rows where index is -1."""
+    if table is None:
+        return None
+    out = table.index_select(0, index.clamp(min=0))
+    return out.masked_fill_((index < 0).view((-1,) + (1,) * (out.dim() - 1)), 0)
+
+
 class PackedDataset:
     def __init__(self, x_all, edge_index_local_all, node_ptr_all, edge_ptr_all, y_all, edge_attr_all=None, edge_label_all=None):
         self.x_all, self.edge_local_all = x_all.contiguous(), edge_index_local_all.contiguous()
@@ -23,6 +38,7 @@ class PackedDataset:
         self.num_graphs = int(node_ptr_all.shape[0]) - 1
         self.node_counts = self.node_ptr_all[1:] - self.node_ptr_all[:-1]
         self.edge_counts = self.edge_ptr_all[1:] - self.edge_ptr_all[:-1]
+        self._capacities = {}
 
     @classmethod
     def from_data_list(cls, graphs: Sequence, device) -> "PackedDataset":
@@ -57,6 +73,54 @@ class PackedDataset:
         take = lambda t, idx: None if t is None else t.index_select(0, idx)
         return Batch(x=self.x_all.index_select(0, node_src), edge_index=edge_index, batch=batch, y=take(self.y_all, ids),
                      edge_attr=take(self.edge_attr_all, edge_src), edge_label=take(self.edge_label_all, edge_src), num_graphs=G)
+
+
+    def capacity_for(self, batch_size: int) -> tuple:
+        """(N_cap, E_cap) that no batch of ``batch_size`` distinct graphs exceeds: the sums of the ``batch_size`` largest node counts
+        (+ 2 padding nodes) and edge counts.  One host read the first time a batch size is asked for."""
+        k = min(int(batch_size), self.num_graphs)
+        if k < 1:
+            raise ValueError("capacity_for needs a batch of at least one graph")
+        if k not in self._capacities:
+            n, e = torch.stack([self.node_counts.topk(k).values.sum(), self.edge_counts.topk(k).values.sum()]).tolist()
+            self._capacities[k] = (int(n) + 2, int(e))
+        return self._capacities[k]
+
+    def collate_padded(self, graph_ids: torch.Tensor, capacity: tuple) -> PaddedBatch:
+        """``collate(graph_ids)`` into tensors of the fixed shape ``capacity = (N_cap, E_cap)``: rows < N_real, slots < E_real and graphs
+        < B are bit-identical to ``collate``; the remaining rows are zero-feature nodes of a padding graph ``B`` and the remaining slots
+        a symmetric edge set among them (include/gsat_hip.h: gsat_collate_padded).  At least two padding nodes always remain.  A batch
+        that does not fit raises ValueError -- in sync-free mode nothing is read back: ``valid[3]`` is set and the batch is all padding.
+        No host decision is taken, so the call can be captured into a hipGraph; run the model on the result through
+        ``GSAT.forward_pass`` or inside ``dp_gsat_amd.padded(batch.valid, batch.capacity)``."""
+        from .graph_index import sync_free
+        ids = graph_ids.to(self.x_all.device, torch.int64).contiguous()
+        B, dev = int(ids.shape[0]), ids.device
+        N_cap, E_cap = int(capacity[0]), int(capacity[1])
+        if B < 1 or N_cap < 2 or E_cap < 0:
+            raise ValueError("collate_padded needs at least one graph and a capacity of at least two nodes")
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        out_node_ptr = torch.cat([zero, self.node_counts[ids].cumsum(0)])
+        out_edge_ptr = torch.cat([zero, self.edge_counts[ids].cumsum(0)])
+        batch = torch.empty(N_cap, dtype=torch.int64, device=dev)
+        node_src = torch.empty(N_cap, dtype=torch.int64, device=dev)
+        edge_index = torch.empty(2, E_cap, dtype=torch.int64, device=dev)
+        edge_src = torch.empty(E_cap, dtype=torch.int64, device=dev)
+        valid = torch.empty(4, dtype=torch.int32, device=dev)
+        call("gsat_collate_padded", ptr(ids), B, ptr(self.node_ptr_all), ptr(self.edge_ptr_all), ptr(self.edge_local_all),
+             int(self.edge_local_all.shape[1]), ptr(out_node_ptr), ptr(out_edge_ptr), N_cap, E_cap, ptr(batch), ptr(node_src),
+             ptr(edge_index) if E_cap else None, ptr(edge_src) if E_cap else None, ptr(valid), stream())
+        if not sync_free():
+            n, e, _, overflow = valid.tolist()           # the one host read, where collate reads its sizes
+            if overflow:
+                raise ValueError(f"collate_padded: the batch does not fit the capacity (N_cap, E_cap) = ({N_cap}, {E_cap}) "
+                                 "(two padding nodes must remain)")
+        y = None
+        if self.y_all is not None:
+            y = torch.cat([self.y_all.index_select(0, ids), self.y_all.new_zeros((1,) + tuple(self.y_all.shape[1:]))])
+        return PaddedBatch(x=_take_padded(self.x_all, node_src), edge_index=edge_index, batch=batch, y=y,
+                           edge_attr=_take_padded(self.edge_attr_all, edge_src), edge_label=_take_padded(self.edge_label_all, edge_src),
+                           num_graphs=B + 1, valid=valid, capacity=(N_cap, E_cap), node_src_row=node_src, edge_src_slot=edge_src)
 
 
 def line_graph(edge_index: torch.Tensor, num_nodes: int, batch: Optional[torch.Tensor] = None):

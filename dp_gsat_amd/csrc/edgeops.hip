@@ -62,11 +62,18 @@ __device__ __forceinline__ float info_dterm(float a, float r) {
     return logf(t1) + a / (r * t1) - logf(t2) - (1.f - a) / (q * t2);
 }
 
-// block partial sums of the info-loss terms; partial[b] in block order
+// entries that count: all M, or the first *m_valid (clamped to [0, M]) of a fixed-capacity batch
+__device__ __forceinline__ int64_t counted_entries(const int32_t* __restrict__ m_valid, int64_t M) {
+    return m_valid ? min<int64_t>(max<int64_t>(*m_valid, 0), M) : M;
+}
+
+// block partial sums of the info-loss terms; partial[b] in block order.  r_dev (one device float) overrides r_scalar.
 __global__ __launch_bounds__(EB) void k_info_partial(const float* __restrict__ att, const float* __restrict__ r_vec, float r_scalar,
-                                                     int64_t M, int64_t per_block, float* __restrict__ partial) {
+                                                     int64_t M, int64_t per_block, float* __restrict__ partial,
+                                                     const int32_t* __restrict__ m_valid = nullptr, const float* __restrict__ r_dev = nullptr) {
     __shared__ float sm[EB];
-    const int64_t beg = (int64_t)blockIdx.x * per_block, end = min(M, beg + per_block);
+    const int64_t beg = (int64_t)blockIdx.x * per_block, end = min(counted_entries(m_valid, M), beg + per_block);
+    if (r_dev) r_scalar = *r_dev;
     float acc = 0.f;
     for (int64_t m = beg + threadIdx.x; m < end; m += EB) acc += info_term(att[m], r_vec ? r_vec[m] : r_scalar);
     sm[threadIdx.x] = acc;
@@ -78,8 +85,10 @@ __global__ __launch_bounds__(EB) void k_info_partial(const float* __restrict__ a
     if (threadIdx.x == 0) partial[blockIdx.x] = sm[0];
 }
 
-__global__ __launch_bounds__(EB) void k_info_final(const float* __restrict__ partial, int nb, float inv_m, float* __restrict__ out) {
+__global__ __launch_bounds__(EB) void k_info_final(const float* __restrict__ partial, int nb, float inv_m, float* __restrict__ out,
+                                                   const int32_t* __restrict__ m_valid = nullptr, int64_t M = 0) {
     __shared__ float sm[EB];
+    if (m_valid) inv_m = 1.f / (float)max<int64_t>(counted_entries(m_valid, M), 1);
     float acc = 0.f;
     for (int i = threadIdx.x; i < nb; i += EB) acc += partial[i];
     sm[threadIdx.x] = acc;
@@ -92,9 +101,14 @@ __global__ __launch_bounds__(EB) void k_info_final(const float* __restrict__ par
 }
 
 __global__ void k_info_bwd(const float* __restrict__ att, const float* __restrict__ r_vec, float r_scalar, const float* __restrict__ gout,
-                           int64_t M, float inv_m, float* __restrict__ datt) {
+                           int64_t M, float inv_m, float* __restrict__ datt, const int32_t* __restrict__ m_valid = nullptr,
+                           const float* __restrict__ r_dev = nullptr) {
     int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m < M) datt[m] = gout[0] * inv_m * info_dterm(att[m], r_vec ? r_vec[m] : r_scalar);
+    if (m >= M) return;
+    const int64_t counted = counted_entries(m_valid, M);
+    if (m_valid) inv_m = 1.f / (float)max<int64_t>(counted, 1);
+    if (r_dev) r_scalar = *r_dev;
+    datt[m] = m < counted ? gout[0] * inv_m * info_dterm(att[m], r_vec ? r_vec[m] : r_scalar) : 0.f;
 }
 
 __global__ void k_narrow(const int64_t* __restrict__ in, int64_t n, int32_t* __restrict__ out) {
@@ -183,6 +197,28 @@ int gsat_info_loss_bwd(const float* att, const float* r_vec, float r_scalar, con
     return GSAT_OK;
 }
 
+int gsat_info_loss_valid_fwd(const float* att, const float* r_vec, float r_scalar, const float* r_dev, int64_t M, const int32_t* m_valid_dev,
+                             float* partial /* [1024] */, float* out, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(M > 0 && att && partial && out && m_valid_dev, GSAT_ERR_ARG, "gsat_info_loss_valid_fwd: bad argument");
+    int nb = (int)std::min<int64_t>(1024, ceil_div(M, EB * 4));
+    int64_t per_block = ceil_div(M, nb);
+    nb = (int)ceil_div(M, per_block);
+    k_info_partial<<<nb, EB, 0, stream>>>(att, r_vec, r_scalar, M, per_block, partial, m_valid_dev, r_dev);
+    k_info_final<<<1, EB, 0, stream>>>(partial, nb, 0.f, out, m_valid_dev, M);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_info_loss_valid_bwd(const float* att, const float* r_vec, float r_scalar, const float* r_dev, const float* gout, int64_t M,
+                             const int32_t* m_valid_dev, float* datt, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(M > 0 && att && gout && datt && m_valid_dev, GSAT_ERR_ARG, "gsat_info_loss_valid_bwd: bad argument");
+    k_info_bwd<<<GRID1(M)>>>(att, r_vec, r_scalar, gout, M, 0.f, datt, m_valid_dev, r_dev);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
 int gsat_narrow_i64(const int64_t* in, int64_t n, int32_t* out, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     GSAT_REQUIRE(n >= 0, GSAT_ERR_ARG, "gsat_narrow_i64: bad n");
@@ -234,9 +270,70 @@ __global__ void k_collate_edges(const int64_t* __restrict__ ids, const int64_t* 
     edge_index[E + e] = edge_local_all[E_all + slot] + off;
 }
 
+// Fixed-capacity batch: the real part as k_collate_*, then padding nodes (graph id G, source row -1) and a symmetric padding edge set
+// among them (source slot -1).  Thread i takes node row i and edge slot i; thread 0 writes valid = (N_real, E_real, G, overflow).
+// A batch that does not fit (fewer than two padding nodes left, or more edges than slots) becomes all padding with overflow = 1.
+__global__ void k_collate_padded(const int64_t* __restrict__ ids, const int64_t* __restrict__ node_ptr_all,
+                                 const int64_t* __restrict__ edge_ptr_all, const int64_t* __restrict__ edge_local_all, int64_t E_all,
+                                 const int64_t* __restrict__ out_node_ptr, const int64_t* __restrict__ out_edge_ptr, int G, int64_t N_cap,
+                                 int64_t E_cap, int64_t* __restrict__ batch, int64_t* __restrict__ node_src_row,
+                                 int64_t* __restrict__ edge_index, int64_t* __restrict__ edge_src_slot, int32_t* __restrict__ valid) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t N = out_node_ptr[G], E = out_edge_ptr[G];
+    const bool overflow = N + 2 > N_cap || E > E_cap;
+    if (overflow) N = E = 0;
+    if (i == 0) { valid[0] = (int32_t)N; valid[1] = (int32_t)E; valid[2] = G; valid[3] = overflow ? 1 : 0; }
+    if (i < N_cap) {
+        if (i < N) {
+            const int g = seg_of(out_node_ptr, G, i);
+            batch[i] = g;
+            node_src_row[i] = node_ptr_all[ids[g]] + (i - out_node_ptr[g]);
+        } else {
+            batch[i] = G;
+            node_src_row[i] = -1;
+        }
+    }
+    if (i < E_cap) {
+        if (i < E) {
+            const int g = seg_of(out_edge_ptr, G, i);
+            const int64_t slot = edge_ptr_all[ids[g]] + (i - out_edge_ptr[g]);
+            const int64_t off = out_node_ptr[g];
+            edge_src_slot[i] = slot;
+            edge_index[i] = edge_local_all[slot] + off;
+            edge_index[E_cap + i] = edge_local_all[E_all + slot] + off;
+        } else {
+            // pair q joins padding nodes q % n_pad and (q + 1) % n_pad, forward in the even slot and back in the odd one; an odd
+            // count ends in a self loop, so the padding set is symmetric whatever its size
+            const int64_t n_pad = N_cap - N, e_pad = E_cap - E, j = i - E, q = j >> 1;
+            const int64_t a = N + q % n_pad, b = N + (q + 1) % n_pad;
+            const bool loop = j == e_pad - 1 && (e_pad & 1);
+            const bool fwd = (j & 1) == 0;
+            edge_src_slot[i] = -1;
+            edge_index[i] = fwd ? a : b;
+            edge_index[E_cap + i] = loop ? a : (fwd ? b : a);
+        }
+    }
+}
+
 }  // namespace gsat
 
 extern "C" {
+
+int gsat_collate_padded(const int64_t* graph_ids, int64_t num_graphs, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
+                        const int64_t* edge_local_all, int64_t num_edges_all, const int64_t* out_node_ptr, const int64_t* out_edge_ptr,
+                        int64_t N_cap, int64_t E_cap, int64_t* batch, int64_t* node_src_row, int64_t* edge_index, int64_t* edge_src_slot,
+                        int32_t* valid, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(num_graphs >= 1 && num_graphs < (1ll << 31) - 1 && N_cap >= 2 && N_cap < (1ll << 31) && E_cap >= 0 && E_cap < (1ll << 31),
+                 GSAT_ERR_ARG, "gsat_collate_padded: bad extents (at least one graph, two padding nodes)");
+    GSAT_REQUIRE(graph_ids && node_ptr_all && edge_ptr_all && out_node_ptr && out_edge_ptr && batch && node_src_row && valid &&
+                 (E_cap == 0 || (edge_local_all && edge_index && edge_src_slot)), GSAT_ERR_ARG, "gsat_collate_padded: null pointer");
+    gsat::k_collate_padded<<<GRID1(std::max(N_cap, E_cap))>>>(graph_ids, node_ptr_all, edge_ptr_all, edge_local_all, num_edges_all, out_node_ptr,
+                                                              out_edge_ptr, (int)num_graphs, N_cap, E_cap, batch, node_src_row, edge_index,
+                                                              edge_src_slot, valid);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
 
 int gsat_collate(const int64_t* graph_ids, int64_t num_graphs, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
                  const int64_t* edge_local_all, int64_t num_edges_all, const int64_t* out_node_ptr, const int64_t* out_edge_ptr,

@@ -24,6 +24,11 @@ struct Tail {                 // what follows act(BN(x)): + residual, then inver
     }
 };
 
+// rows that count: all N, or the first *n_valid (clamped to [0, N]) of a fixed-capacity batch whose tail rows are padding
+__device__ __forceinline__ int64_t counted_rows(const int32_t* __restrict__ n_valid, int64_t N) {
+    return n_valid ? min<int64_t>(max<int64_t>(*n_valid, 0), N) : N;
+}
+
 __device__ __forceinline__ float4 nslot_reduce(float4 v, float4 (*sm)[NL], int slot, int lane) {
     __syncthreads();
     sm[slot][lane] = v;
@@ -54,12 +59,13 @@ __device__ __forceinline__ float4 block_colsum(const float* __restrict__ part, i
 // MODE 0: part[rb,c] = sum_rows x ; MODE 1: sum_rows (x - mean)^2
 template <int MODE>
 __global__ __launch_bounds__(NB) void k_bn_partial(const float* __restrict__ x, int64_t N, int C, int64_t rows_per_block,
-                                                   const float* __restrict__ mean, float* __restrict__ part) {
+                                                   const float* __restrict__ mean, float* __restrict__ part,
+                                                   const int32_t* __restrict__ n_valid = nullptr) {
     __shared__ float4 sm[NS][NL];
     const int lane = threadIdx.x % NL, slot = threadIdx.x / NL;
     const int c = (blockIdx.x * NL + lane) * 4;
     const bool on = c < C;
-    const int64_t beg = (int64_t)blockIdx.y * rows_per_block, end = min(N, beg + rows_per_block);
+    const int64_t beg = (int64_t)blockIdx.y * rows_per_block, end = min(counted_rows(n_valid, N), beg + rows_per_block);
     const float4 mu = (MODE == 1 && on) ? ld4(mean + c) : f4zero();
     float4 acc = f4zero();
     if (on)
@@ -79,13 +85,14 @@ __global__ __launch_bounds__(NB) void k_bn_partial(const float* __restrict__ x, 
 // the block's ~200 rows from L2), and leaves (mean_b, M2_b) per channel; k_bn_finalize_chan combines the blocks pairwise-exactly (Chan et al.:
 // delta = mean_b - mean; mean += delta n_b / n; M2 += M2_b + delta^2 n_a n_b / n) in fixed order.  As accurate as the two-pass scheme it
 // replaces (no E[x^2] - mean^2 cancellation), with one sweep over HBM and three launches (partial, finalize, apply) instead of five.
-__global__ __launch_bounds__(NB) void k_bn_partial_chan(const float* __restrict__ x, int64_t N, int C, int64_t rows_per_block, float* __restrict__ part) {
+__global__ __launch_bounds__(NB) void k_bn_partial_chan(const float* __restrict__ x, int64_t N, int C, int64_t rows_per_block, float* __restrict__ part,
+                                                        const int32_t* __restrict__ n_valid) {
     __shared__ float4 sm[NS][NL];
     __shared__ float4 smean[NL];
     const int lane = threadIdx.x % NL, slot = threadIdx.x / NL;
     const int c = (blockIdx.x * NL + lane) * 4;
     const bool on = c < C;
-    const int64_t beg = (int64_t)blockIdx.y * rows_per_block, end = min(N, beg + rows_per_block);
+    const int64_t beg = (int64_t)blockIdx.y * rows_per_block, end = min(counted_rows(n_valid, N), beg + rows_per_block);   // a block past the count: no rows, (0, 0)
     const float inv = 1.f / (float)max<int64_t>(end - beg, 1);
     float4 acc = f4zero();
     if (on)
@@ -119,7 +126,9 @@ __device__ __forceinline__ void chan_add(Chan4& a, float4 mb, float4 m2b, float 
 }
 __global__ __launch_bounds__(NB) void k_bn_finalize_chan(const float* __restrict__ part, int RB, int64_t N, int64_t rows_per_block, int C, float eps,
                                                          float momentum, float* __restrict__ mean, float* __restrict__ rstd,
-                                                         float* __restrict__ running_mean, float* __restrict__ running_var) {
+                                                         float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                         const int32_t* __restrict__ n_valid) {
+    N = counted_rows(n_valid, N);
     __shared__ float4 smu[NS][NL], sm2[NS][NL];
     __shared__ float sn[NS];
     const int lane = threadIdx.x % NL, slot = threadIdx.x / NL;
@@ -137,7 +146,7 @@ __global__ __launch_bounds__(NB) void k_bn_finalize_chan(const float* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int r = r0 + j * NS;
-            if (r < RB) chan_add(a, mb[j], qb[j], (float)(min(N, (int64_t)(r + 1) * rows_per_block) - (int64_t)r * rows_per_block));
+            if (r < RB) chan_add(a, mb[j], qb[j], (float)(min(N, (int64_t)(r + 1) * rows_per_block) - (int64_t)r * rows_per_block));    // <= 0: skipped
         }
     }
     smu[slot][lane] = a.mean; sm2[slot][lane] = a.m2;
@@ -145,7 +154,7 @@ __global__ __launch_bounds__(NB) void k_bn_finalize_chan(const float* __restrict
     __syncthreads();
     if (slot != 0 || !on) return;
     for (int s = 1; s < NS; ++s) chan_add(a, smu[s][lane], sm2[s][lane], sn[s]);          // then the sixteen slot results, in slot order
-    const float inv = 1.f / (float)N;
+    const float inv = 1.f / (float)max<int64_t>(N, 1);
     st4(mean + c, a.mean);
     st4(rstd + c, make_float4(1.f / sqrtf(a.m2.x * inv + eps), 1.f / sqrtf(a.m2.y * inv + eps), 1.f / sqrtf(a.m2.z * inv + eps), 1.f / sqrtf(a.m2.w * inv + eps)));
     if (running_mean) {
@@ -162,14 +171,15 @@ __global__ __launch_bounds__(NB) void k_bn_finalize_chan(const float* __restrict
 template <int STAGE>
 __global__ __launch_bounds__(NB) void k_bn_finalize(const float* __restrict__ part, int RB, int64_t N, int C, float eps, float momentum,
                                                     float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ running_mean,
-                                                    float* __restrict__ running_var) {
+                                                    float* __restrict__ running_var, const int32_t* __restrict__ n_valid) {
     __shared__ float4 sm[NS][NL];
     const int lane = threadIdx.x % NL, slot = threadIdx.x / NL;
     const int c = (blockIdx.x * NL + lane) * 4;
     const bool on = c < C;
     float4 t = block_colsum(part, RB, C, c, on, sm, slot, lane);
     if (slot != 0 || !on) return;
-    const float inv = 1.f / (float)N;
+    N = counted_rows(n_valid, N);
+    const float inv = 1.f / (float)max<int64_t>(N, 1);
     if (STAGE == 0) {
         st4(mean + c, make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv));
     } else {
@@ -220,12 +230,12 @@ __global__ void k_bn_apply(const float* __restrict__ x, const float* __restrict_
 __global__ __launch_bounds__(NB) void k_bn_bwd_partial(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
                                                        const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, int64_t N, int C, int relu, int64_t rows_per_block,
-                                                       Tail tail, float* __restrict__ part) {
+                                                       Tail tail, float* __restrict__ part, const int32_t* __restrict__ n_valid = nullptr) {
     __shared__ float4 sm[NS][NL];
     const int lane = threadIdx.x % NL, slot = threadIdx.x / NL;
     const int c = (blockIdx.x * NL + lane) * 4;
     const bool on = c < C;
-    const int64_t beg = (int64_t)blockIdx.y * rows_per_block, end = min(N, beg + rows_per_block);
+    const int64_t beg = (int64_t)blockIdx.y * rows_per_block, end = min(counted_rows(n_valid, N), beg + rows_per_block);
     float4 a1 = f4zero(), a2 = f4zero();
     if (on) {
         const float4 mu = ld4(mean + c), rs = ld4(rstd + c), g = ld4(gamma + c), b = ld4(beta + c);
@@ -264,10 +274,18 @@ __global__ __launch_bounds__(NB) void k_bn_bwd_finalize(const float* __restrict_
 __global__ void k_bn_bwd_apply(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
                                const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
                                const float* __restrict__ dbeta, const float* __restrict__ dgamma, int64_t N, int C, int relu, int training,
-                               Tail tail, float* __restrict__ dx, float* __restrict__ dres, float inv_n, const float* __restrict__ rows_dev) {
+                               Tail tail, float* __restrict__ dx, float* __restrict__ dres, float inv_n, const float* __restrict__ rows_dev,
+                               const int32_t* __restrict__ n_valid = nullptr) {
     const int C4 = C >> 2;
     if (rows_dev) inv_n = 1.f / *rows_dev;            // global row count of a sharded batch, still on the device
+    const int64_t rows = counted_rows(n_valid, N), counted = rows * C4;
+    if (n_valid) inv_n = 1.f / (float)max<int64_t>(rows, 1);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N * C4; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i >= counted) {                               // padding rows: exact zeros, so nothing leaks into the dW of the Linear in front
+            st4(dx + i * 4, f4zero());
+            if (dres) st4(dres + i * 4, f4zero());
+            continue;
+        }
         const int c = (int)(i % C4) * 4;
         float4 v = ld4(x + i * 4), d = ld4(dy + i * 4), mu = ld4(mean + c), rs = ld4(rstd + c), g = ld4(gamma + c), b = ld4(beta + c);
         if (tail.p > 0.f) { const float4 k = tail.keep_scale(i / C4, c); d = make_float4(d.x * k.x, d.y * k.y, d.z * k.z, d.w * k.w); }
@@ -308,10 +326,11 @@ size_t gsat_bn_workspace_floats(int64_t N, int64_t C) {
     return (size_t)RB * (size_t)C * 2;
 }
 
-int gsat_bn_act_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t N, int64_t C,
-                    int training, float momentum, float eps, int relu, const float* residual, float dropout_p, uint64_t seed,
-                    const uint64_t* seed_dev, float* y, float* save_mean, float* save_rstd, float* workspace, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// n_valid (device, or NULL = all N rows): the rows the training statistics and the backward sums run over (gsat_bn_act_*_valid)
+static int bn_act_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t N, int64_t C,
+                      int training, float momentum, float eps, int relu, const float* residual, float dropout_p, uint64_t seed,
+                      const uint64_t* seed_dev, float* y, float* save_mean, float* save_rstd, float* workspace, const int32_t* n_valid,
+                      hipStream_t stream) {
     GSAT_REQUIRE(N >= 0 && C > 0 && C % 4 == 0 && N < (1ll << 31), GSAT_ERR_UNSUPPORTED, "gsat_bn_fwd: C must be a positive multiple of 4");
     GSAT_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, GSAT_ERR_ARG, "gsat_bn_act_fwd: dropout_p must be in [0, 1)");
     if (N == 0) return GSAT_OK;
@@ -326,13 +345,13 @@ int gsat_bn_act_fwd(const float* x, const float* gamma, const float* beta, float
         const unsigned ct = (unsigned)ceil_div(C, 64);
         static const int one_pass = getenv("GSAT_BN_ONE_PASS") ? atoi(getenv("GSAT_BN_ONE_PASS")) : 1;
         if (one_pass) {
-            k_bn_partial_chan<<<grid, NB, 0, stream>>>(x, N, (int)C, rpb, workspace);
-            k_bn_finalize_chan<<<ct, NB, 0, stream>>>(workspace, (int)RB, N, rpb, (int)C, eps, momentum, save_mean, save_rstd, running_mean, running_var);
+            k_bn_partial_chan<<<grid, NB, 0, stream>>>(x, N, (int)C, rpb, workspace, n_valid);
+            k_bn_finalize_chan<<<ct, NB, 0, stream>>>(workspace, (int)RB, N, rpb, (int)C, eps, momentum, save_mean, save_rstd, running_mean, running_var, n_valid);
         } else {
-        k_bn_partial<0><<<grid, NB, 0, stream>>>(x, N, (int)C, rpb, nullptr, part0);
-        k_bn_finalize<0><<<ct, NB, 0, stream>>>(part0, (int)RB, N, (int)C, eps, momentum, save_mean, save_rstd, running_mean, running_var);
-        k_bn_partial<1><<<grid, NB, 0, stream>>>(x, N, (int)C, rpb, save_mean, part1);
-        k_bn_finalize<1><<<ct, NB, 0, stream>>>(part1, (int)RB, N, (int)C, eps, momentum, save_mean, save_rstd, running_mean, running_var);
+        k_bn_partial<0><<<grid, NB, 0, stream>>>(x, N, (int)C, rpb, nullptr, part0, n_valid);
+        k_bn_finalize<0><<<ct, NB, 0, stream>>>(part0, (int)RB, N, (int)C, eps, momentum, save_mean, save_rstd, running_mean, running_var, n_valid);
+        k_bn_partial<1><<<grid, NB, 0, stream>>>(x, N, (int)C, rpb, save_mean, part1, n_valid);
+        k_bn_finalize<1><<<ct, NB, 0, stream>>>(part1, (int)RB, N, (int)C, eps, momentum, save_mean, save_rstd, running_mean, running_var, n_valid);
         }
     } else {
         GSAT_REQUIRE(running_mean && running_var, GSAT_ERR_ARG, "gsat_bn_fwd: eval mode needs running statistics");
@@ -344,6 +363,22 @@ int gsat_bn_act_fwd(const float* x, const float* gamma, const float* beta, float
     return GSAT_OK;
 }
 
+int gsat_bn_act_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t N, int64_t C,
+                    int training, float momentum, float eps, int relu, const float* residual, float dropout_p, uint64_t seed,
+                    const uint64_t* seed_dev, float* y, float* save_mean, float* save_rstd, float* workspace, void* stream_) {
+    return bn_act_fwd(x, gamma, beta, running_mean, running_var, N, C, training, momentum, eps, relu, residual, dropout_p, seed, seed_dev, y,
+                      save_mean, save_rstd, workspace, nullptr, (hipStream_t)stream_);
+}
+
+int gsat_bn_act_fwd_valid(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t N, int64_t C,
+                          int training, float momentum, float eps, int relu, const float* residual, float dropout_p, uint64_t seed,
+                          const uint64_t* seed_dev, float* y, float* save_mean, float* save_rstd, float* workspace,
+                          const int32_t* n_valid_dev, void* stream_) {
+    GSAT_REQUIRE(n_valid_dev, GSAT_ERR_ARG, "gsat_bn_act_fwd_valid: null row count");
+    return bn_act_fwd(x, gamma, beta, running_mean, running_var, N, C, training, momentum, eps, relu, residual, dropout_p, seed, seed_dev, y,
+                      save_mean, save_rstd, workspace, n_valid_dev, (hipStream_t)stream_);
+}
+
 int gsat_bn_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t N, int64_t C,
                 int training, float momentum, float eps, int relu, float* y, float* save_mean, float* save_rstd, float* workspace,
                 void* stream_) {
@@ -351,10 +386,9 @@ int gsat_bn_fwd(const float* x, const float* gamma, const float* beta, float* ru
                            save_mean, save_rstd, workspace, stream_);
 }
 
-int gsat_bn_act_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,
-                    int64_t N, int64_t C, int training, int relu, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dx,
-                    float* dresidual, float* dgamma, float* dbeta, float* workspace, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+static int bn_act_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,
+                      int64_t N, int64_t C, int training, int relu, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dx,
+                      float* dresidual, float* dgamma, float* dbeta, float* workspace, const int32_t* n_valid, hipStream_t stream) {
     GSAT_REQUIRE(N >= 0 && C > 0 && C % 4 == 0 && N < (1ll << 31), GSAT_ERR_UNSUPPORTED, "gsat_bn_bwd: C must be a positive multiple of 4");
     GSAT_REQUIRE(dgamma && dbeta, GSAT_ERR_ARG, "gsat_bn_bwd: null gradient output");
     GSAT_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, GSAT_ERR_ARG, "gsat_bn_act_bwd: dropout_p must be in [0, 1)");
@@ -367,12 +401,27 @@ int gsat_bn_act_bwd(const float* x, const float* dy, const float* gamma, const f
     int64_t RB, rpb;
     row_blocks(N, &RB, &rpb);
     const Tail tail{nullptr, dropout_p, SeedRef{seed, seed_dev}};
-    k_bn_bwd_partial<<<dim3((unsigned)ceil_div(C, 64), (unsigned)RB), NB, 0, stream>>>(x, dy, save_mean, save_rstd, gamma, beta, N, (int)C, relu, rpb, tail, workspace);
+    k_bn_bwd_partial<<<dim3((unsigned)ceil_div(C, 64), (unsigned)RB), NB, 0, stream>>>(x, dy, save_mean, save_rstd, gamma, beta, N, (int)C, relu, rpb, tail, workspace, n_valid);
     k_bn_bwd_finalize<<<(unsigned)ceil_div(C, 64), NB, 0, stream>>>(workspace, (int)RB, (int)C, dbeta, dgamma);
     k_bn_bwd_apply<<<ew_grid(N * (C / 4)), 256, 0, stream>>>(x, dy, save_mean, save_rstd, gamma, beta, dbeta, dgamma, N, (int)C, relu, training, tail, dx, dresidual,
-                                                              1.f / (float)N, nullptr);
+                                                              1.f / (float)N, nullptr, n_valid);
     GSAT_LAUNCH_CHECK();
     return GSAT_OK;
+}
+
+int gsat_bn_act_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,
+                    int64_t N, int64_t C, int training, int relu, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dx,
+                    float* dresidual, float* dgamma, float* dbeta, float* workspace, void* stream_) {
+    return bn_act_bwd(x, dy, gamma, beta, save_mean, save_rstd, N, C, training, relu, dropout_p, seed, seed_dev, dx, dresidual, dgamma, dbeta,
+                      workspace, nullptr, (hipStream_t)stream_);
+}
+
+int gsat_bn_act_bwd_valid(const float* x, const float* dy, const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,
+                          int64_t N, int64_t C, int training, int relu, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dx,
+                          float* dresidual, float* dgamma, float* dbeta, float* workspace, const int32_t* n_valid_dev, void* stream_) {
+    GSAT_REQUIRE(n_valid_dev, GSAT_ERR_ARG, "gsat_bn_act_bwd_valid: null row count");
+    return bn_act_bwd(x, dy, gamma, beta, save_mean, save_rstd, N, C, training, relu, dropout_p, seed, seed_dev, dx, dresidual, dgamma, dbeta,
+                      workspace, n_valid_dev, (hipStream_t)stream_);
 }
 
 int gsat_bn_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,

@@ -90,6 +90,8 @@ class DualGSAT(nn.Module):
     def dual_forward_pass(self, primal_data, dual_data, epoch, training, primal_noise=None, dual_noise=None,
                           primal_masks=None, dual_masks=None):
         from .graph_index import get_index
+        if getattr(primal_data, "valid", None) is not None or getattr(dual_data, "valid", None) is not None:
+            raise ValueError("DualGSAT does not take padded batches (PackedDataset.collate_padded): use collate")
         for d in (primal_data, dual_data):
             if getattr(d, "num_graphs", None) is not None:      # prime the segment cache without `batch.max()` (a host sync)
                 get_index(d.edge_index, d.x.shape[0]).graphs(d.batch, int(d.num_graphs))

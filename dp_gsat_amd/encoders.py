@@ -6,6 +6,7 @@ import torch.nn as nn
 
 from .graph_index import get_index
 from .ops import BatchNormFn, EmbeddingSum, SyncBatchNormFn, linear, segment_pool
+from .padding import current_padding
 
 # [3P] ogb 1.3.2 get_atom_feature_dims() / get_bond_feature_dims()
 ATOM_FEATURE_DIMS = [119, 5, 12, 12, 10, 6, 6, 2, 2]
@@ -68,6 +69,15 @@ class BatchNorm1d(nn.BatchNorm1d):
         hip_ok = shape_ok and x.shape[0] > 0
         p = float(dropout_p) if self.training else 0.0
         sync = None
+        pad = current_padding()
+        n_valid = None
+        if pad is not None:        # a padded batch: statistics over its real rows only, and no path that would count the padding
+            if self.sync_group is not None:
+                raise ValueError("BatchNorm1d with sync_group cannot take a padded batch (data-parallel statistics are not count-aware)")
+            if not hip_ok:
+                raise ValueError("BatchNorm1d inside padded() needs a 2-D fp32 ROCm input with affine parameters and a channel count "
+                                 f"that is a multiple of 4 (got {tuple(x.shape)}, {x.dtype}, device {x.device})")
+            n_valid = pad.node_rows(x.shape[0], "BatchNorm1d")
         if (self.training or not self.track_running_stats) and self.sync_group is not None:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
@@ -103,7 +113,7 @@ class BatchNorm1d(nn.BatchNorm1d):
                                          residual, p, seed, seed_dev, sync[0])
         return BatchNormFn.apply(x, self.weight, self.bias, self.running_mean if self.track_running_stats else None,
                                  self.running_var if self.track_running_stats else None, training, self.momentum, self.eps, fused_relu,
-                                 residual, p, seed, seed_dev)
+                                 residual, p, seed, seed_dev, n_valid)
 
 
 class BatchNorm(nn.Module):

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from .get_model import MLP
 from .graph_index import get_index, sync_free
+from .padding import current_padding, padded
 from .ops import ExtractorAttention, InfoLoss, Lift, LiftedAttention, Sample, Symmetrise, device_seed, edge_tensor, new_seed
 
 
@@ -124,9 +125,17 @@ def symmetrise_edge_att(att, edge_index, num_nodes):
     return att
 
 
-def info_loss(att, r):
-    """example/gsat.py:31 ; src/run_gsat.py:127,132 (tensor prior allowed, detached)."""
-    return InfoLoss.apply(edge_tensor(att), edge_tensor(r))
+def info_loss(att, r, r_dev=None, edge=None):
+    """example/gsat.py:31 ; src/run_gsat.py:127,132 (tensor prior allowed, detached).  Inside ``padded()`` the mean runs over the real
+    attention entries (``edge``: edge- or node-attention; told by the length when the capacities differ) and ``r_dev``, one float on the
+    device, replaces the scalar ``r``."""
+    a = edge_tensor(att)
+    pad = current_padding()
+    if pad is None:
+        if r_dev is not None:
+            raise ValueError("a device r is only taken inside padded()")
+        return InfoLoss.apply(a, edge_tensor(r))
+    return InfoLoss.apply(a, edge_tensor(r), pad.attention_rows(a.numel(), edge), r_dev)
 
 
 class GSAT(nn.Module):
@@ -145,10 +154,13 @@ class GSAT(nn.Module):
         self.decay_r = decay_r
         self.sync_loss_dict = True       # the reference calls .item() three times per step (example/gsat.py:34)
 
-    def __loss__(self, att, clf_logits, clf_labels, epoch, loss_weights=None):
+    def __loss__(self, att, clf_logits, clf_labels, epoch, loss_weights=None, r_dev=None):
         pred_loss = self.criterion(clf_logits, clf_labels)
         r = self.get_r(self.decay_interval, self.decay_r, epoch, final_r=self.final_r)
-        i_loss = info_loss(att, r)
+        if current_padding() is None:
+            i_loss = info_loss(att, r)
+        else:
+            i_loss = info_loss(att, r, r_dev, edge=bool(self.learn_edge_att))
         if loss_weights is None:
             loss = pred_loss + i_loss
         else:       # data-parallel shards: dist.global_loss_weights() makes the averaged gradients those of the global batch
@@ -163,7 +175,20 @@ class GSAT(nn.Module):
     def forward_pass(self, data, epoch, training, noise=None, dropout_masks=None, loss_weights=None):
         """Returns (edge_att, loss, loss_dict, clf_logits) like the reference.  ``noise`` / ``dropout_masks``
         optionally pin the randomness (same-seed parity is impossible against torch's CPU generator); ``loss_weights``
-        = (graph weight, attention-row weight) of a data-parallel shard (dp_gsat_amd.dist.global_loss_weights)."""
+        = (graph weight, attention-row weight) of a data-parallel shard (dp_gsat_amd.dist.global_loss_weights).
+
+        A padded batch (one with a ``valid`` field, PackedDataset.collate_padded) runs inside ``padded(data.valid)``: BatchNorm and the info
+        loss count its real rows, the criterion sees the real graphs ``[:B]``, and ``data.r`` -- one float on the device, when present -- is
+        the info loss's r instead of get_r(epoch).  Every returned tensor has capacity shape; callers slice with the counts."""
+        valid = getattr(data, "valid", None)
+        if valid is not None:
+            if getattr(self.criterion, "multi_label", False):
+                raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
+            with padded(valid, (int(data.x.shape[0]), int(data.edge_index.shape[1]))):
+                return self._forward_pass(data, epoch, training, noise, dropout_masks, loss_weights, int(data.num_graphs) - 1)
+        return self._forward_pass(data, epoch, training, noise, dropout_masks, loss_weights, None)
+
+    def _forward_pass(self, data, epoch, training, noise, dropout_masks, loss_weights, real_graphs):
         N = data.x.shape[0]
         num_graphs = getattr(data, "num_graphs", None)
         if num_graphs is not None:      # PyG batches know their graph count: prime the segment cache without `batch.max()` (a sync)
@@ -177,7 +202,11 @@ class GSAT(nn.Module):
         else:
             edge_att = self.lift_node_att_to_edge_att(att, data.edge_index)
         clf_logits = self.clf(data.x, data.edge_index, data.batch, edge_attr=data.edge_attr, edge_atten=edge_att)
-        loss, loss_dict = self.__loss__(att, clf_logits, data.y, epoch, loss_weights)
+        if real_graphs is None:
+            loss, loss_dict = self.__loss__(att, clf_logits, data.y, epoch, loss_weights)
+        else:           # static slices: the padding graph is the last one and B is a host int
+            loss, loss_dict = self.__loss__(att, clf_logits[:real_graphs], data.y[:real_graphs], epoch, loss_weights,
+                                            r_dev=getattr(data, "r", None))
         return edge_att, loss, loss_dict, clf_logits
 
     @staticmethod

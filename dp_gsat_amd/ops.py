@@ -600,10 +600,12 @@ class Symmetrise(torch.autograd.Function):
 
 
 class InfoLoss(torch.autograd.Function):
-    """mean(att*log(att/r+1e-6) + (1-att)*log((1-att)/(1-r+1e-6)+1e-6)); r scalar or detached tensor prior."""
+    """mean(att*log(att/r+1e-6) + (1-att)*log((1-att)/(1-r+1e-6)+1e-6)); r scalar or detached tensor prior.
+    ``m_valid`` (one int32 on the device): the mean runs over the first m_valid entries of a padded batch and the rest get a zero
+    gradient; ``r_dev`` (one float on the device) then replaces the scalar ``r``, so a captured step follows the r schedule."""
 
     @staticmethod
-    def forward(ctx, att, r):
+    def forward(ctx, att, r, m_valid=None, r_dev=None):
         a = _f32c(att)
         r_vec = _f32c(r.detach()) if isinstance(r, torch.Tensor) else None
         r_scalar = 0.0 if r_vec is not None else float(r)
@@ -611,9 +613,17 @@ class InfoLoss(torch.autograd.Function):
             raise ValueError("tensor prior must have one entry per attention value")
         out = torch.empty((), dtype=torch.float32, device=a.device)
         partial = torch.empty(1024, dtype=torch.float32, device=a.device)
-        call("gsat_info_loss_fwd", ptr(a), ptr(r_vec), r_scalar, a.numel(), ptr(partial), ptr(out), stream())
+        if m_valid is None:
+            if r_dev is not None:
+                raise ValueError("a device r needs the count-aware info loss (m_valid)")
+            call("gsat_info_loss_fwd", ptr(a), ptr(r_vec), r_scalar, a.numel(), ptr(partial), ptr(out), stream())
+        else:
+            if r_dev is not None and (r_vec is not None or r_dev.dtype != torch.float32 or r_dev.numel() != 1):
+                raise ValueError("r_dev must be one float32 on the device, without a tensor prior")
+            call("gsat_info_loss_valid_fwd", ptr(a), ptr(r_vec), r_scalar, ptr(r_dev), a.numel(), ptr(m_valid), ptr(partial), ptr(out), stream())
         ctx.save_for_backward(a, r_vec if r_vec is not None else a.new_empty(0))
         ctx.r_scalar, ctx.has_vec = r_scalar, r_vec is not None
+        ctx.m_valid, ctx.r_dev = m_valid, r_dev
         return out
 
     @staticmethod
@@ -621,8 +631,12 @@ class InfoLoss(torch.autograd.Function):
         a, r_vec = ctx.saved_tensors
         gout = _f32c(gout)
         da = torch.empty_like(a)
-        call("gsat_info_loss_bwd", ptr(a), ptr(r_vec if ctx.has_vec else None), ctx.r_scalar, ptr(gout), a.numel(), ptr(da), stream())
-        return da, None
+        if ctx.m_valid is None:
+            call("gsat_info_loss_bwd", ptr(a), ptr(r_vec if ctx.has_vec else None), ctx.r_scalar, ptr(gout), a.numel(), ptr(da), stream())
+        else:
+            call("gsat_info_loss_valid_bwd", ptr(a), ptr(r_vec if ctx.has_vec else None), ctx.r_scalar, ptr(ctx.r_dev), ptr(gout), a.numel(),
+                 ptr(ctx.m_valid), ptr(da), stream())
+        return da, None, None, None
 
 
 class InstanceNormFn(torch.autograd.Function):
@@ -694,11 +708,12 @@ class BatchNormFn(torch.autograd.Function):
     """BatchNorm1d over rows with optional fused ReLU (src/models/gin.py:58, src/models/pna.py:45,57) and, for PNA, the rest of
     the layer tail in the same passes: y = dropout_p(relu(BN(x)) + residual)  (src/models/pna.py:57-59).  The dropout mask is
     Philox stream 3 keyed by (seed, row, column); ``seed_dev`` (a 1-element int64 device tensor) replaces the host seed in
-    sync-free / hipGraph mode."""
+    sync-free / hipGraph mode.  ``n_valid`` (one int32 on the device): statistics, backward sums and 1/n over the first n_valid rows of a
+    padded batch, exact zero gradients on the rest."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, relu, residual=None, dropout_p=0.0,
-                seed=0, seed_dev=None):
+                seed=0, seed_dev=None, n_valid=None):
         from ._lib import load
         x, weight, bias, residual = _f32c(x), _f32c(weight), _f32c(bias), _f32c(residual)
         N, C = x.shape
@@ -708,9 +723,13 @@ class BatchNormFn(torch.autograd.Function):
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         rstd = torch.empty(C, dtype=torch.float32, device=x.device)
         ws = torch.empty(max(int(load().gsat_bn_workspace_floats(N, C)), 1), dtype=torch.float32, device=x.device)
-        call("gsat_bn_act_fwd", ptr(x), ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var), N, C, int(training),
-             float(momentum), float(eps), int(relu), ptr(residual), float(dropout_p), int(seed), ptr(seed_dev), ptr(y), ptr(mean),
-             ptr(rstd), ptr(ws), stream())
+        args = (ptr(x), ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var), N, C, int(training), float(momentum), float(eps),
+                int(relu), ptr(residual), float(dropout_p), int(seed), ptr(seed_dev), ptr(y), ptr(mean), ptr(rstd), ptr(ws))
+        if n_valid is None:
+            call("gsat_bn_act_fwd", *args, stream())
+        else:
+            call("gsat_bn_act_fwd_valid", *args, ptr(n_valid), stream())
+        ctx.n_valid = n_valid
         ctx.save_for_backward(x, weight, bias, mean, rstd)
         ctx.flags = (bool(training), bool(relu), float(dropout_p), int(seed), residual is not None)
         ctx.seed_dev = seed_dev
@@ -727,9 +746,13 @@ class BatchNormFn(torch.autograd.Function):
         dres = torch.empty_like(x) if has_res and ctx.needs_input_grad[9] else None
         dgamma, dbeta = torch.empty_like(weight), torch.empty_like(bias)
         ws = torch.empty(max(int(load().gsat_bn_workspace_floats(N, C)), 1), dtype=torch.float32, device=x.device)
-        call("gsat_bn_act_bwd", ptr(x), ptr(dy), ptr(weight), ptr(bias), ptr(mean), ptr(rstd), N, C, int(training), int(relu),
-             dropout_p, seed, ptr(ctx.seed_dev), ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta), ptr(ws), stream())
-        return dx, dgamma, dbeta, None, None, None, None, None, None, dres, None, None, None
+        args = (ptr(x), ptr(dy), ptr(weight), ptr(bias), ptr(mean), ptr(rstd), N, C, int(training), int(relu), dropout_p, seed,
+                ptr(ctx.seed_dev), ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta), ptr(ws))
+        if ctx.n_valid is None:
+            call("gsat_bn_act_bwd", *args, stream())
+        else:
+            call("gsat_bn_act_bwd_valid", *args, ptr(ctx.n_valid), stream())
+        return dx, dgamma, dbeta, None, None, None, None, None, None, dres, None, None, None, None
 
 
 class SyncBatchNormFn(torch.autograd.Function):

@@ -10,7 +10,11 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
   * data parallelism (optional): `python -m torch.distributed.run --nproc-per-node N examples/train_ba2motifs.py` shards every
     global batch over the ranks by edge count (LPT), re-weights the local losses and all-reduces one flat gradient buffer.
 
+  * dp_gsat_amd.ReplayedStep (``--graph``, single process) -- every full batch is collated to a fixed capacity and trained by replaying
+    ONE captured hipGraph (collation, forward, backward, fused Adam); the tail batch of an epoch runs eagerly.
+
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
 """
 import argparse
 import os
@@ -61,9 +65,12 @@ def main():
     ap.add_argument("--backbone", default="GIN", choices=["GIN", "PNA"])
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, one GPU per rank) or gloo (to rehearse N ranks on one GPU)")
+    ap.add_argument("--graph", action="store_true", help="train full batches as replays of one captured hipGraph (single process)")
     args = ap.parse_args()
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if args.graph and world > 1:
+        ap.error("--graph is single-process: it replays one captured step and cannot shard a batch over ranks")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     if world > 1:
@@ -86,7 +93,7 @@ def main():
     clf = G.get_model(10, 0, 2, False, cfg, dev)
     ext = G.ExtractorMLP(args.hidden, True).to(dev)
     params = list(clf.parameters()) + list(ext.parameters())
-    opt = torch.optim.Adam(params, lr=1e-3, weight_decay=3e-6)
+    opt = torch.optim.Adam(params, lr=1e-3, weight_decay=3e-6, **(dict(capturable=True, fused=True) if args.graph else {}))
     gsat = G.GSAT(clf, ext, G.Criterion(2, False), opt, learn_edge_att=True)
     flat = FlatGradAllReduce(params) if world > 1 else None
     torch.manual_seed(args.seed + 1000 * rank)                    # independent noise / dropout per rank from here on
@@ -103,12 +110,19 @@ def main():
                                  G.precision_at_k(att, b.edge_label, 5, b.batch, b.edge_index, b.num_graphs).double().mean()]).tolist()
         return acc, auc, prec
 
+    replayed = None
+    if args.graph and n_train >= args.batch_size:
+        replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
+
     gen = np.random.RandomState(args.seed)                        # identical permutations on every rank
     for epoch in range(args.epochs):
         perm = gen.permutation(n_train)
         tot, nb = 0.0, 0
         for s in range(0, n_train, args.batch_size):
             ids = perm[s:s + args.batch_size]
+            if replayed is not None and len(ids) == args.batch_size:
+                tot, nb = tot + replayed.step(ids, epoch), nb + 1   # the loss stays on the device: no host read per step
+                continue
             if world > 1:                                         # whole graphs to ranks, balanced by edge count
                 ids = ids[shard_graphs_lpt(edge_counts[ids], world)[rank]]
             b = ds.collate(torch.as_tensor(ids, device=dev))
@@ -126,7 +140,7 @@ def main():
             tot, nb = tot + ld["loss"], nb + 1
         if rank == 0 and (epoch % 5 == 4 or epoch == args.epochs - 1):
             acc, auc, prec = evaluate(np.arange(n_train, len(graphs)))
-            print(f"epoch {epoch + 1:3d}  train loss {tot / nb:.4f}  test acc {acc:.3f}  attention ROC-AUC vs motif edges {auc:.3f}  prec@5 {prec:.3f}",
+            print(f"epoch {epoch + 1:3d}  train loss {float(tot) / nb:.4f}  test acc {acc:.3f}  attention ROC-AUC vs motif edges {auc:.3f}  prec@5 {prec:.3f}",
                   flush=True)
     if world > 1:
         dist.destroy_process_group()

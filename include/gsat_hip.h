@@ -336,6 +336,22 @@ int gsat_bn_act_bwd(const float* x, const float* dy, const float* gamma, const f
                     float* dbeta, float* workspace, void* stream);
 
 /*
+ * The same two calls for a fixed-capacity batch whose rows >= *n_valid_dev (one int32 on the device, clamped to [0, N]) are padding:
+ * training mean / biased variance / running statistics (unbiased factor n / max(n - 1, 1)) over the first n = *n_valid_dev rows on
+ * both statistics paths; y is written for every row with the same formula.  Backward: sum dy and sum dy xhat, dgamma and dbeta from the
+ * counted rows, dx with 1 / max(n, 1); rows >= n of dx and dresidual are exact zeros.  Eval mode ignores the count.  The dropout
+ * mask is keyed by row, so a counted row draws what it draws in the unpadded batch.
+ */
+int gsat_bn_act_fwd_valid(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          int64_t N, int64_t C, int training, float momentum, float eps, int relu, const float* residual,
+                          float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* y, float* save_mean,
+                          float* save_rstd, float* workspace, const int32_t* n_valid_dev, void* stream);
+int gsat_bn_act_bwd_valid(const float* x, const float* dy, const float* gamma, const float* beta, const float* save_mean,
+                          const float* save_rstd, int64_t N, int64_t C, int training, int relu, float dropout_p,
+                          uint64_t seed, const uint64_t* seed_dev, float* dx, float* dresidual, float* dgamma,
+                          float* dbeta, float* workspace, const int32_t* n_valid_dev, void* stream);
+
+/*
  * BatchNorm over a batch that is sharded across ranks: the same kernels in separate steps, with the two tiny cross-rank
  * reductions left to the caller (torch.distributed all-reduce of [C] vectors), so a sharded run reproduces the single-process
  * statistics at the same global batch:
@@ -555,6 +571,16 @@ int gsat_info_loss_fwd(const float* att, const float* r_vec, float r_scalar, int
 int gsat_info_loss_bwd(const float* att, const float* r_vec, float r_scalar, const float* gout, int64_t M,
                        float* datt, void* stream);
 
+/*
+ * The info loss of a fixed-capacity batch: the mean runs over the first m = *m_valid_dev entries (int32 on the device, clamped to
+ * [0, M]; the divisor is max(m, 1)), datt[k] = 0 exactly for k >= m.  r_dev (one float on the device, may be NULL) overrides r_scalar,
+ * so the get_r(epoch) schedule can change between replays of a captured step.
+ */
+int gsat_info_loss_valid_fwd(const float* att, const float* r_vec, float r_scalar, const float* r_dev, int64_t M,
+                             const int32_t* m_valid_dev, float* partial, float* out, void* stream);
+int gsat_info_loss_valid_bwd(const float* att, const float* r_vec, float r_scalar, const float* r_dev, const float* gout,
+                             int64_t M, const int32_t* m_valid_dev, float* datt, void* stream);
+
 /* out[i] = (int32) in[i] */
 int gsat_narrow_i64(const int64_t* in, int64_t n, int32_t* out, void* stream);
 
@@ -574,6 +600,19 @@ int gsat_collate(const int64_t* graph_ids, int64_t num_graphs, const int64_t* no
                  const int64_t* edge_local_all, int64_t num_edges_all, const int64_t* out_node_ptr,
                  const int64_t* out_edge_ptr, int64_t N, int64_t E, int64_t* batch, int64_t* node_src_row,
                  int64_t* edge_index, int64_t* edge_src_slot, void* stream);
+
+/*
+ * gsat_collate into tensors of fixed capacity (batch / node_src_row [N_cap], edge_index [2, E_cap], edge_src_slot [E_cap]): one launch.
+ * Rows < N_real and slots < E_real (the last entries of out_node_ptr / out_edge_ptr, read on the device) are what gsat_collate writes.
+ * Padding nodes get graph id num_graphs and source row -1.  Padding slot E_real + j (source slot -1) joins the padding nodes
+ * a = N_real + q % n_pad and b = N_real + (q + 1) % n_pad, q = j / 2: a -> b for even j, b -> a for odd j, and the self loop a -> a in
+ * the last slot of an odd count -- a symmetric set that touches no real node.  valid (int32[4]) = (N_real, E_real, num_graphs, overflow).
+ * N_real + 2 > N_cap or E_real > E_cap: overflow = 1 and an all-padding batch (N_real = E_real = 0); nothing is written out of bounds.
+ */
+int gsat_collate_padded(const int64_t* graph_ids, int64_t num_graphs, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
+                        const int64_t* edge_local_all, int64_t num_edges_all, const int64_t* out_node_ptr,
+                        const int64_t* out_edge_ptr, int64_t N_cap, int64_t E_cap, int64_t* batch, int64_t* node_src_row,
+                        int64_t* edge_index, int64_t* edge_src_slot, int32_t* valid, void* stream);
 
 /*
  * Line ("dual") graph: dual node k = primal directed edge k; dual edges join, in both directions, every two primal
