@@ -12,10 +12,10 @@ from .pna import PNA
 from .spmotif_gnn import SPMotifNet
 from .gsat import (GSAT, ExtractorMLP, concrete_sample, get_r, gumbel_sigmoid, info_loss,
                    lift_node_att_to_edge_att, symmetrise_edge_att)
-from .collate import PackedDataset, PaddedBatch, line_graph, line_graph_undirected
+from .collate import PackedDataset, PaddedBatch, collate_padded_pair, line_graph, line_graph_undirected
 from .padding import current_padding, padded
-from .replay import ReplayedStep
-from .dual_gsat import DualGSAT, f1_sparsity_loss
+from .replay import ReplayedDualStep, ReplayedStep
+from .dual_gsat import DualGSAT, f1_sparsity_loss, f1_sparsity_loss_valid
 from .graph_index import BatchIndex, clear_cache, get_index, set_strict, set_sync_free
 from .utils import process_data, reorder_like, set_seed
 from .explain import EdgeRanking, ExplanationMeter, attention_auroc, delta_kl, precision_at_k, rank_edges, topk_edge_mask
@@ -30,4 +30,5 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "EdgeRanking", "ExplanationMeter", "attention_auroc", "delta_kl", "precision_at_k", "rank_edges", "topk_edge_mask",
            "SubgraphBatch", "edge_subgraph", "node_subgraph", "explanation_subgraph", "explanation_fidelity", "gather_rows",
            "AttentionHistogram", "EvaluationMeter", "attention_histogram", "classifier_accuracy", "classifier_rocauc", "pr_curve",
-           "task_auroc_counts", "PaddedBatch", "padded", "current_padding", "ReplayedStep"]
+           "task_auroc_counts", "PaddedBatch", "padded", "current_padding", "ReplayedStep",
+           "ReplayedDualStep", "collate_padded_pair", "f1_sparsity_loss_valid"]

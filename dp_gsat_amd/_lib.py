@@ -89,6 +89,10 @@ SIGNATURES = {
     "gsat_info_loss_bwd": (INT, [P, P, F32, P, I64, P, P]),
     "gsat_info_loss_valid_fwd": (INT, [P, P, F32, P, I64, P, P, P, P]),
     "gsat_info_loss_valid_bwd": (INT, [P, P, F32, P, P, I64, P, P, P]),
+    "gsat_f1_sparsity_fwd": (INT, [P, P, I64, P, P, P, P, P]),
+    "gsat_f1_sparsity_bwd": (INT, [P, P, P, P, I64, P, P, P]),
+    "gsat_f1_sparsity_block_entries": (I64, []),
+    "gsat_f1_sparsity_max_blocks": (I64, []),
     "gsat_collate_padded": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P, P]),
     "gsat_collate": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P]),
     "gsat_line_graph_pair_counts": (INT, [P, I64, P, P]),

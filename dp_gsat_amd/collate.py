@@ -19,7 +19,8 @@ class PaddedBatch(Batch):
     """A batch of fixed capacity (``PackedDataset.collate_padded``): the ``B`` real graphs first, then one padding graph ``B`` that holds
     the unused node rows and edge slots, so ``num_graphs = B + 1``.  Besides the fields of ``collate``'s batch it carries ``valid``
     (int32[4] on the device: N_real, E_real, B, overflow), ``capacity = (N_cap, E_cap)``, ``node_src_row`` / ``edge_src_slot`` (the
-    dataset row / slot of every node / edge, -1 for padding) and optionally ``r`` (one device float: the info loss's r)."""
+    dataset row / slot of every node / edge, -1 for padding) and optionally ``r`` (one device float: the info loss's r) and ``pair`` (the
+    other batch of a ``collate_padded_pair``)."""
 
 
 def _take_padded(table, index):
@@ -86,6 +87,53 @@ class PackedDataset:
             self._capacities[k] = (int(n) + 2, int(e))
         return self._capacities[k]
 
+    def pair_capacity_for(self, dual: "PackedDataset", batch_size: int) -> tuple:
+        """(N_cap, E_cap, E_dual_cap) of ``collate_padded_pair`` that no batch of ``batch_size`` distinct graphs exceeds: ``capacity_for`` of
+        this (primal) dataset and the sum of the ``batch_size`` largest dual edge counts.  The dual node capacity is always E_cap + 2."""
+        n, e = self.capacity_for(batch_size)
+        return (n, e, dual.capacity_for(batch_size)[1])
+
+    def check_pair(self, dual: "PackedDataset") -> None:
+        """Raise ValueError unless ``dual`` has one node per edge of this dataset, graph by graph (one host read; remembered)."""
+        if getattr(dual, "_primal", None) is self:
+            return
+        if dual.num_graphs != self.num_graphs or not bool(torch.equal(dual.node_counts, self.edge_counts.to(dual.node_counts.device))):
+            raise ValueError("not a dual of this dataset: its graphs' node counts must be this dataset's edge counts "
+                             "(PackedDataset.line_graph_dataset builds one)")
+        dual._primal = self
+
+    def line_graph_dataset(self, dual_x: Optional[torch.Tensor] = None) -> "PackedDataset":
+        """The dual dataset: graph g is the directed line graph (``line_graph``'s rule) of graph g; its node k is primal edge k of graph g,
+        so ``node_counts`` are this dataset's ``edge_counts`` and ``collate_padded_pair`` lines primal edge slots up with dual node rows.
+        Dual edges carry ids local to their graph, ``y`` is shared.  ``dual_x`` [E_all, F]: dual node features; default [x[src] || x[dst]]
+        (float ``x`` only).  Built by ONE line-graph pass over the whole packed dataset and one host read (the dual's size)."""
+        from .graph_index import BatchIndex
+        dev = self.x_all.device
+        G, N_all, E_all = self.num_graphs, int(self.x_all.shape[0]), int(self.edge_local_all.shape[1])
+        edge_graph = torch.repeat_interleave(torch.arange(G, device=dev), self.edge_counts, output_size=E_all)
+        ei = (self.edge_local_all + self.node_ptr_all[edge_graph]).contiguous()                 # global node ids
+        ix = BatchIndex(ei, N_all)                  # local: the index of a whole dataset has no place in the per-batch cache
+        counts = torch.empty(N_all, dtype=torch.int64, device=dev)
+        call("gsat_line_graph_pair_counts", ptr(ix.rowptr_src), N_all, ptr(counts), stream())
+        pair_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), counts.cumsum(0)])
+        num_pairs, fewest = torch.stack([pair_ptr[-1], self.edge_counts.min() if G else pair_ptr[-1] + 1]).tolist()
+        if G and fewest == 0:
+            raise ValueError("a graph without edges has an empty line graph: drop it before building the dual dataset")
+        dual_ei = torch.empty(2, 2 * num_pairs, dtype=torch.int64, device=dev)
+        call("gsat_line_graph", ptr(ix.rowptr_src), ptr(ix.eid_by_src), ptr(pair_ptr), N_all, num_pairs, ptr(dual_ei), stream())
+        # dual edges come out by source node, hence graph by graph: graph g owns the pairs of its nodes
+        dual_edge_ptr = 2 * pair_ptr[self.node_ptr_all]
+        dual_local = dual_ei - self.edge_ptr_all[edge_graph[dual_ei[0]]]
+        if dual_x is None:
+            if not self.x_all.is_floating_point():
+                raise ValueError("line_graph_dataset: pass dual_x for a dataset with categorical node features")
+            dual_x = torch.cat([self.x_all[ei[0]], self.x_all[ei[1]]], dim=1)
+        elif int(dual_x.shape[0]) != E_all:
+            raise ValueError("dual_x needs one row per primal edge")
+        dual = PackedDataset(dual_x.to(dev), dual_local, self.edge_ptr_all, dual_edge_ptr, self.y_all)
+        dual._primal = self
+        return dual
+
     def collate_padded(self, graph_ids: torch.Tensor, capacity: tuple) -> PaddedBatch:
         """``collate(graph_ids)`` into tensors of the fixed shape ``capacity = (N_cap, E_cap)``: rows < N_real, slots < E_real and graphs
         < B are bit-identical to ``collate``; the remaining rows are zero-feature nodes of a padding graph ``B`` and the remaining slots
@@ -93,6 +141,12 @@ class PackedDataset:
         that does not fit raises ValueError -- in sync-free mode nothing is read back: ``valid[3]`` is set and the batch is all padding.
         No host decision is taken, so the call can be captured into a hipGraph; run the model on the result through
         ``GSAT.forward_pass`` or inside ``dp_gsat_amd.padded(batch.valid, batch.capacity)``."""
+        return self._collate_padded(graph_ids, capacity)
+
+    def _collate_padded(self, graph_ids, capacity, spoil=None, check=True) -> PaddedBatch:
+        """``collate_padded``; ``spoil`` (a 0-dim bool on the device) makes the batch an overflow whatever its size -- the joint verdict of a
+        pair: the node total handed to the kernel is raised by the capacity, which fails its ``N + 2 <= N_cap`` test, and an overflow
+        batch reads neither scan.  ``check=False`` leaves the host read of the overflow word to the caller."""
         from .graph_index import sync_free
         ids = graph_ids.to(self.x_all.device, torch.int64).contiguous()
         B, dev = int(ids.shape[0]), ids.device
@@ -102,6 +156,8 @@ class PackedDataset:
         zero = torch.zeros(1, dtype=torch.int64, device=dev)
         out_node_ptr = torch.cat([zero, self.node_counts[ids].cumsum(0)])
         out_edge_ptr = torch.cat([zero, self.edge_counts[ids].cumsum(0)])
+        if spoil is not None:
+            out_node_ptr[B] += spoil.to(torch.int64) * N_cap
         batch = torch.empty(N_cap, dtype=torch.int64, device=dev)
         node_src = torch.empty(N_cap, dtype=torch.int64, device=dev)
         edge_index = torch.empty(2, E_cap, dtype=torch.int64, device=dev)
@@ -110,7 +166,7 @@ class PackedDataset:
         call("gsat_collate_padded", ptr(ids), B, ptr(self.node_ptr_all), ptr(self.edge_ptr_all), ptr(self.edge_local_all),
              int(self.edge_local_all.shape[1]), ptr(out_node_ptr), ptr(out_edge_ptr), N_cap, E_cap, ptr(batch), ptr(node_src),
              ptr(edge_index) if E_cap else None, ptr(edge_src) if E_cap else None, ptr(valid), stream())
-        if not sync_free():
+        if check and not sync_free():
             n, e, _, overflow = valid.tolist()           # the one host read, where collate reads its sizes
             if overflow:
                 raise ValueError(f"collate_padded: the batch does not fit the capacity (N_cap, E_cap) = ({N_cap}, {E_cap}) "
@@ -121,6 +177,32 @@ class PackedDataset:
         return PaddedBatch(x=_take_padded(self.x_all, node_src), edge_index=edge_index, batch=batch, y=y,
                            edge_attr=_take_padded(self.edge_attr_all, edge_src), edge_label=_take_padded(self.edge_label_all, edge_src),
                            num_graphs=B + 1, valid=valid, capacity=(N_cap, E_cap), node_src_row=node_src, edge_src_slot=edge_src)
+
+
+def collate_padded_pair(primal: PackedDataset, dual: PackedDataset, graph_ids: torch.Tensor, capacity: Optional[tuple] = None):
+    """``(pb, db)``: the graphs ``graph_ids`` of a dataset and of its dual (``primal.line_graph_dataset()``) as fixed-capacity batches that
+    line up -- ``pb = primal.collate_padded(ids, (N_cap, E_cap))`` and ``db = dual.collate_padded(ids, (E_cap + 2, E_dual_cap))``, so dual
+    node row k < E_cap is primal edge slot k (the + 2: the padding nodes every padded batch keeps).  ``capacity = (N_cap, E_cap,
+    E_dual_cap)`` defaults to ``primal.pair_capacity_for(dual, len(graph_ids))``.  ``pb.pair is db`` and ``db.pair is pb``:
+    ``DualGSAT.dual_forward_pass`` takes padded batches only as such a pair.
+
+    Overflow is joint and decided on the device: if either batch does not fit, BOTH are all padding with ``valid[3] == 1`` (ValueError
+    outside sync-free mode, after one host read)."""
+    from .graph_index import sync_free
+    primal.check_pair(dual)
+    ids = torch.as_tensor(graph_ids).to(primal.x_all.device, torch.int64).contiguous()
+    if capacity is None:
+        capacity = primal.pair_capacity_for(dual, int(ids.shape[0]))
+    N_cap, E_cap, Ed_cap = (int(c) for c in capacity)
+    n, e, ed = primal.node_counts[ids].sum(), primal.edge_counts[ids].sum(), dual.edge_counts[ids].sum()
+    spoil = (n + 2 > N_cap) | (e > E_cap) | (ed > Ed_cap)
+    pb = primal._collate_padded(ids, (N_cap, E_cap), spoil, check=False)
+    db = dual._collate_padded(ids, (E_cap + 2, Ed_cap), spoil, check=False)
+    pb.pair, db.pair = db, pb
+    if not sync_free() and int(pb.valid[3]):
+        raise ValueError(f"collate_padded_pair: the batch does not fit the capacity (N_cap, E_cap, E_dual_cap) = ({N_cap}, {E_cap}, {Ed_cap}) "
+                         "(two padding nodes must remain)")
+    return pb, db
 
 
 def line_graph(edge_index: torch.Tensor, num_nodes: int, batch: Optional[torch.Tensor] = None):

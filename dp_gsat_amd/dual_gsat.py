@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from .get_model import Criterion
-from .ops import Sample
+from .ops import F1SparsityLoss, InfoLoss, Sample, edge_tensor
+from .padding import padded
 from .gsat import (concrete_sample, get_r, gumbel_sigmoid, info_loss, lift_node_att_to_edge_att,
                    symmetrise_edge_att)
 
@@ -30,6 +31,14 @@ def f1_sparsity_loss(p_uv, y_uv, eps=1e-6):
     recall = TP / (G + eps)
     f1 = 2 * precision * recall / (precision + recall + eps)
     return (1 - f1) + p_uv.abs().mean()
+
+
+def f1_sparsity_loss_valid(p, y, m_valid=None):
+    """``f1_sparsity_loss`` as two HIP launches (one more for the backward) over the first ``m_valid`` entries -- one int32 on the device,
+    e.g. ``batch.valid[1:2]`` of a padded batch; None counts every entry.  Entries beyond the count are not read (NaN there is harmless)
+    and get a zero gradient; a count of 0 gives the loss 1 and zero gradients; ``y`` gets no gradient.  Bitwise repeatable and
+    capturable into a hipGraph."""
+    return F1SparsityLoss.apply(p, y.detach().float(), m_valid)
 
 
 class DualGSAT(nn.Module):
@@ -91,7 +100,10 @@ class DualGSAT(nn.Module):
                           primal_masks=None, dual_masks=None):
         from .graph_index import get_index
         if getattr(primal_data, "valid", None) is not None or getattr(dual_data, "valid", None) is not None:
-            raise ValueError("DualGSAT does not take padded batches (PackedDataset.collate_padded): use collate")
+            if getattr(primal_data, "pair", None) is not dual_data or getattr(dual_data, "pair", None) is not primal_data:
+                raise ValueError("DualGSAT takes padded batches only as a pair from collate_padded_pair (whose primal edge slots and dual "
+                                 "node rows line up): use it, or collate")
+            return self._pair_forward_pass(primal_data, dual_data, epoch, training, primal_noise, dual_noise, primal_masks, dual_masks)
         for d in (primal_data, dual_data):
             if getattr(d, "num_graphs", None) is not None:      # prime the segment cache without `batch.max()` (a host sync)
                 get_index(d.edge_index, d.x.shape[0]).graphs(d.batch, int(d.num_graphs))
@@ -122,6 +134,66 @@ class DualGSAT(nn.Module):
                                         primal_data.y, dual_data.y, dual_att_log_logits, epoch)                # :276
         loss = loss + f1_loss                                                                                 # :281
         return primal_edge_att, loss, loss_dict, primal_clf_logits
+
+    def _pair_forward_pass(self, pb, db, epoch, training, primal_noise, dual_noise, primal_masks, dual_masks):
+        """``dual_forward_pass`` on a padded pair (collate_padded_pair): dual node row k < Ep is primal edge slot k.  Every primal module runs
+        inside ``padded(pb.valid)``, every dual one inside ``padded(db.valid)``; the whole-batch reductions take their counts from the
+        device (f1 and the primal info loss: pb.valid[1]; the dual info loss: db.valid[1], with ``db.r`` -- one device float, when set --
+        as its r); both criteria see the real graphs ``[:B]``.  No host decision depends on the batch, so the call can be captured; every
+        output has capacity shape."""
+        from .graph_index import get_index
+        if self.primal_learn_edge_att or self.dual_learn_edge_att:
+            raise ValueError("a padded pair takes node attention on both sides (the MUTAG configs), not edge attention")
+        if self.primal_criterion.multi_label or self.dual_criterion.multi_label:
+            raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
+        if pb.edge_label is None:
+            raise ValueError("the f1 sparsity loss needs the primal dataset's edge_label")
+        (Np, Ep), (Nd, Ed) = pb.capacity, db.capacity
+        B = int(pb.num_graphs) - 1
+        if Nd != Ep + 2 or int(db.num_graphs) - 1 != B:
+            raise ValueError("not a padded pair: the dual node capacity must be the primal edge capacity + 2, with the same graphs")
+        pctx, dctx = (lambda: padded(pb.valid, pb.capacity)), (lambda: padded(db.valid, db.capacity))
+        for d in (pb, db):
+            get_index(d.edge_index, d.x.shape[0]).graphs(d.batch, int(d.num_graphs))
+        with pctx():
+            primal_emb = self.primal_clf.get_emb(pb.x, pb.edge_index, batch=pb.batch, edge_attr=pb.edge_attr)
+            if training and primal_noise is None:
+                primal_noise = torch.empty(Np, 1, device=primal_emb.device).uniform_(1e-10, 1 - 1e-10)
+            _, primal_node_att = self.primal_extractor.attend(primal_emb, pb.edge_index, pb.batch, primal_noise if training else None,
+                                                              primal_masks)
+        with dctx():
+            dual_emb = self.dual_clf.get_emb(db.x, db.edge_index, batch=db.batch, edge_attr=db.edge_attr)
+            dual_att_log_logits = self.dual_extractor(dual_emb, db.edge_index, db.batch, dropout_masks=dual_masks)
+        if training or self.gumbel_noise_in_eval:
+            dual_node_att = gumbel_sigmoid(dual_att_log_logits, tau=self.gumbel_tau, noise=dual_noise)
+        else:
+            dual_node_att = Sample.apply(dual_att_log_logits, None, 0, self.gumbel_tau, 0.0)
+        n_edges = pb.valid[1:2]                                                  # = db.valid[0:1]: the real primal edges / dual nodes
+        dual_on_edges = dual_node_att[:Ep]
+        f1_loss = f1_sparsity_loss_valid(dual_on_edges, pb.edge_label, n_edges)
+        dual_edge_att = lift_node_att_to_edge_att(dual_node_att, db.edge_index)
+        primal_edge_att = lift_node_att_to_edge_att(primal_node_att, pb.edge_index)
+        if epoch > self.mix_after_epoch:
+            primal_edge_att = self.mix_alpha * dual_on_edges + (1 - self.mix_alpha) * primal_edge_att
+        with pctx():
+            primal_clf_logits = self.primal_clf(pb.x, pb.edge_index, pb.batch, edge_attr=pb.edge_attr, edge_atten=primal_edge_att)
+        with dctx():
+            dual_clf_logits = self.dual_clf(db.x, db.edge_index, db.batch, edge_attr=db.edge_attr, edge_atten=dual_edge_att)
+        # __loss__ with counts: the same terms, coefficients, order of the sum and loss dict -- change the two together
+        primal_pred_loss = self.primal_criterion(primal_clf_logits[:B], pb.y[:B]) * self.primal_pred_loss_coef
+        dual_pred_loss = self.dual_criterion(dual_clf_logits[:B], db.y[:B]) * self.dual_pred_loss_coef
+        dual_r = self.dual_fix_r if self.dual_fix_r else get_r(self.dual_decay_interval, self.dual_decay_r, epoch,
+                                                                final_r=self.dual_final_r, init_r=self.dual_init_r)
+        dual_info_loss = InfoLoss.apply(edge_tensor(dual_edge_att), dual_r, db.valid[1:2], getattr(db, "r", None)) * self.dual_info_loss_coef
+        prior = dual_att_log_logits.sigmoid().detach()[:Ep]
+        primal_info_loss = InfoLoss.apply(edge_tensor(primal_edge_att), prior, n_edges, None) * self.primal_info_loss_coef
+        loss = primal_pred_loss + dual_pred_loss + primal_info_loss + dual_info_loss
+        if self.sync_loss_dict:
+            v = torch.stack([loss.detach(), dual_pred_loss.detach(), dual_info_loss.detach()]).tolist()
+            loss_dict = {"loss": v[0], "pred": v[1], "info": v[2]}
+        else:
+            loss_dict = {"loss": loss.detach(), "pred": dual_pred_loss.detach(), "info": dual_info_loss.detach()}
+        return primal_edge_att, loss + f1_loss, loss_dict, primal_clf_logits
 
     # -- src/run_gsat.py:612-637 -----------------------------------------------------------------------------------
     def dual_train_one_batch(self, primal_data, dual_data, epoch):

@@ -639,6 +639,35 @@ class InfoLoss(torch.autograd.Function):
         return da, None, None, None
 
 
+class F1SparsityLoss(torch.autograd.Function):
+    """(1 - softF1(p, y)) + mean|p| (src/run_gsat.py:151-180) over the first ``m_valid`` entries (one int32 on the device; None: all).
+    Two launches forward, one backward, bitwise repeatable; entries beyond the count are not read and get a zero gradient; ``y`` gets
+    none."""
+
+    @staticmethod
+    def forward(ctx, p, y, m_valid=None):
+        a, b = _f32c(p), _f32c(y.detach())
+        if a.numel() != b.numel() or a.numel() == 0:
+            raise ValueError("f1 sparsity loss: p and y need the same, non-zero number of entries")
+        if m_valid is not None and (m_valid.dtype != torch.int32 or m_valid.numel() != 1 or not m_valid.is_cuda):
+            raise ValueError("m_valid must be one int32 on the device")
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        stats = torch.empty(8, dtype=torch.float32, device=a.device)
+        partial = torch.empty(1024, dtype=torch.float32, device=a.device)
+        call("gsat_f1_sparsity_fwd", ptr(a), ptr(b), a.numel(), ptr(m_valid), ptr(partial), ptr(out), ptr(stats), stream())
+        ctx.save_for_backward(a, b, stats)
+        ctx.m_valid = m_valid
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b, stats = ctx.saved_tensors
+        gout = _f32c(gout)
+        da = torch.empty_like(a)
+        call("gsat_f1_sparsity_bwd", ptr(a), ptr(b), ptr(stats), ptr(gout), a.numel(), ptr(ctx.m_valid), ptr(da), stream())
+        return da, None, None
+
+
 class InstanceNormFn(torch.autograd.Function):
     """per-graph InstanceNorm (eps 1e-5, no affine, batch statistics always) -- src/utils/get_model.py:50-51."""
 

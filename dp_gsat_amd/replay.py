@@ -137,3 +137,178 @@ class ReplayedStep:
         n, e = torch.stack([ds.node_counts[p].sum(1).max(), ds.edge_counts[p].sum(1).max()]).tolist()
         if n + 2 > self.capacity[0] or e > self.capacity[1]:
             raise ValueError(f"a batch of this epoch needs (N, E) = ({n} + 2 padding nodes, {e}), above the capacity {self.capacity}")
+
+
+class ReplayedDualStep:
+    """``ReplayedDualStep(dual_gsat, primal_ds, dual_ds, batch_size, capacity=None)``: the dual/primal training step (DualGSAT) over a
+    dataset and its dual (``primal_ds.line_graph_dataset()``) as replays of captured hipGraphs.  One replay holds clear_cache,
+    collate_padded_pair, dual_forward_pass, both zero_grad(set_to_none=True), the backward and both optimizer steps.  Both optimizers
+    must be capturable.  Whether the dual attention is mixed into the primal one (``epoch > mix_after_epoch``) is a host branch, so TWO
+    graphs are captured -- unmixed and mixed -- over the same parameters and optimizer state, and ``step(ids, epoch)`` picks one; the
+    unmixed graph is arithmetically the eager step (and keeps PNA's lazy lift).  Three warm-up runs on a side stream precede the
+    captures; parameters, buffers and both optimizers' state are put back afterwards, so capturing does not train.
+
+    ``capacity = (N_cap, E_cap, E_dual_cap)`` defaults to ``primal_ds.pair_capacity_for(dual_ds, batch_size)``.  Overflow is joint
+    (collate_padded_pair) and handled as in ``ReplayedStep``: ``overflowed()`` / ``check_epoch``.
+
+    ``pinned=True``: the graphs read their randomness from static capacity-shaped buffers instead of drawing it -- ``primal_noise``
+    [N_cap, 1] and ``dual_noise`` [E_cap + 2, 1] (uniform), ``primal_masks`` / ``dual_masks`` (the extractors' two dropout keep-masks) --
+    which the caller may overwrite between steps.  The default draws fresh noise inside the graph on every replay.
+
+    After a step: ``loss`` (device scalar), ``clf_logits`` [B + 1, C] (primal), ``batch`` / ``dual_batch`` (the padded pair) and, with
+    ``keep_edge_att=True``, ``edge_att`` [E_cap, 1]; all overwritten by the next replay of the same graph.  ``p.grad`` of every
+    parameter points at the gradients of the graph that ran last.  ``graphs``: an own pair of ``torch.cuda.CUDAGraph`` (unmixed, mixed) to
+    capture into (with debug mode on, to dump them)."""
+
+    def __init__(self, dual_gsat, primal_ds, dual_ds, batch_size: int, capacity: Optional[tuple] = None, pinned: bool = False,
+                 keep_edge_att: bool = False, graphs=None):
+        m = dual_gsat
+        for side, opt in (("primal", m.primal_optimizer), ("dual", m.dual_optimizer)):
+            if opt is None or not all(g.get("capturable", False) for g in opt.param_groups):
+                raise ValueError(f"ReplayedDualStep needs a capturable {side} optimizer, e.g. torch.optim.Adam(params, capturable=True, fused=True)")
+        if m.primal_criterion.multi_label or m.dual_criterion.multi_label:
+            raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
+        if m.primal_learn_edge_att or m.dual_learn_edge_att:
+            raise ValueError("a padded pair takes node attention on both sides (the MUTAG configs), not edge attention")
+        primal_ds.check_pair(dual_ds)
+        self.model, self.primal_ds, self.dual_ds, self.batch_size = m, primal_ds, dual_ds, int(batch_size)
+        if not 1 <= self.batch_size <= primal_ds.num_graphs:
+            raise ValueError("batch_size must be between 1 and the dataset's graph count")
+        cap = capacity if capacity is not None else primal_ds.pair_capacity_for(dual_ds, self.batch_size)
+        self.capacity = tuple(int(c) for c in cap)
+        if len(self.capacity) != 3:
+            raise ValueError("capacity is (N_cap, E_cap, E_dual_cap)")
+        dev = primal_ds.x_all.device
+        self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
+        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
+        self.keep_edge_att, self.pinned = bool(keep_edge_att), bool(pinned)
+        self.primal_noise = self.dual_noise = self.primal_masks = self.dual_masks = None
+        if self.pinned:
+            N_cap, E_cap, _ = self.capacity
+            self.primal_noise = torch.empty(N_cap, 1, device=dev).uniform_(1e-10, 1 - 1e-10)
+            self.dual_noise = torch.rand(E_cap + 2, 1, device=dev)
+            self.primal_masks = self._keep_masks(m.primal_extractor, N_cap, dev)
+            self.dual_masks = self._keep_masks(m.dual_extractor, E_cap + 2, dev)
+        self.batch = self.dual_batch = self.loss = self.clf_logits = self.edge_att = None
+        self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        unmixed, mixed = graphs if graphs is not None else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
+        self.graphs = {False: unmixed, True: mixed}
+        self._outputs, self._grads, self._current = {}, {}, None
+        self._capture()
+
+    @staticmethod
+    def _keep_masks(extractor, rows, dev):
+        l1, l2, _ = extractor.mlp.linears()
+        keep = 1.0 - float(extractor.mlp.dropout_p)
+        return [(torch.rand(rows, int(l.weight.shape[0]), device=dev) < keep).float() for l in (l1, l2)]
+
+    def _r_of(self, epoch):
+        m = self.model
+        return m.dual_fix_r if m.dual_fix_r else get_r(m.dual_decay_interval, m.dual_decay_r, epoch, final_r=m.dual_final_r,
+                                                       init_r=m.dual_init_r)
+
+    def _params(self):
+        return [p for grp in self.model.primal_optimizer.param_groups + self.model.dual_optimizer.param_groups for p in grp["params"]]
+
+    def run_once(self, mixed: bool):
+        """The step body (what one graph holds), run on the current stream."""
+        from .collate import collate_padded_pair
+        m = self.model
+        clear_cache()
+        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
+        db.r = self.r
+        self._overflow.bitwise_or_(pb.valid[3:4])
+        epoch = m.mix_after_epoch + (1 if mixed else 0)           # only the mix reads it: r comes from db.r
+        att, loss, _, logits = m.dual_forward_pass(pb, db, epoch, True, self.primal_noise, self.dual_noise, self.primal_masks,
+                                                   self.dual_masks)
+        m.primal_optimizer.zero_grad(set_to_none=True)
+        m.dual_optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        m.primal_optimizer.step()
+        m.dual_optimizer.step()
+        out = dict(batch=pb, dual_batch=db, loss=loss.detach(), clf_logits=logits.detach(),
+                   edge_att=edge_tensor(att).detach() if self.keep_edge_att else None)
+        self._outputs[mixed] = out
+        self._grads[mixed] = [p.grad for p in self._params()]
+        self._select(mixed)
+
+    def _select(self, mixed):
+        for k, v in self._outputs[mixed].items():
+            setattr(self, k, v)
+        if self._current is not mixed:
+            for p, g in zip(self._params(), self._grads[mixed]):
+                p.grad = g
+            self._current = mixed
+
+    def _capture(self):
+        m = self.model
+        opts = (m.primal_optimizer, m.dual_optimizer)
+        tensors = list(m.parameters()) + list(m.buffers())
+        saved = [t.detach().clone() for t in tensors]
+        had_state = {id(p): {k: v.clone() for k, v in opt.state[p].items() if isinstance(v, torch.Tensor)}
+                     for opt in opts for grp in opt.param_groups for p in grp["params"] if p in opt.state}
+        was_sync_free, was_loss_dict = sync_free(), m.sync_loss_dict
+        set_sync_free(True)
+        m.sync_loss_dict = False
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for mixed in (False, True, False):          # both bodies run eagerly before either is captured
+                    self.run_once(mixed)
+            torch.cuda.current_stream().wait_stream(side)
+            if int(self.batch.valid[3]) != 0:
+                raise ValueError(f"ReplayedDualStep: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
+            for mixed in (False, True):                     # no reseeding in between: both graphs draw from the one device seed stream
+                self._current = None
+                with torch.cuda.graph(self.graphs[mixed]):
+                    self.run_once(mixed)
+        finally:
+            set_sync_free(was_sync_free)
+            m.sync_loss_dict = was_loss_dict
+            clear_cache()
+            with torch.no_grad():          # also when capturing failed; in place: the graphs hold these addresses
+                for t, s in zip(tensors, saved):
+                    t.copy_(s)
+                for opt in opts:
+                    for grp in opt.param_groups:
+                        for p in grp["params"]:
+                            for k, v in opt.state.get(p, {}).items():
+                                if isinstance(v, torch.Tensor):
+                                    old = had_state.get(id(p), {}).get(k)
+                                    v.copy_(old) if old is not None else v.zero_()
+                self._overflow.zero_()
+
+    def step(self, graph_ids, epoch: int) -> torch.Tensor:
+        """One training step on the graphs ``graph_ids`` (exactly ``batch_size`` ids) at ``epoch``: the dual r follows its schedule and the
+        mixed graph runs when ``epoch > mix_after_epoch``.  Returns the device loss; nothing is read back."""
+        ids = torch.as_tensor(graph_ids)
+        if ids.numel() != self.batch_size:
+            raise ValueError(f"ReplayedDualStep was captured for {self.batch_size} graphs per step, got {ids.numel()}")
+        self.graph_ids.copy_(ids.reshape(-1), non_blocking=True)
+        self.r.fill_(float(self._r_of(epoch)))
+        mixed = bool(epoch > self.model.mix_after_epoch)
+        self.graphs[mixed].replay()
+        self._select(mixed)
+        return self.loss
+
+    def overflowed(self) -> bool:
+        """True if a step since the last call (or since capture) got a pair that did not fit the capacity.  One host read; clears the flag."""
+        seen = bool(int(self._overflow))
+        self._overflow.zero_()
+        return seen
+
+    def check_epoch(self, perm) -> None:
+        """Raise ValueError if a full batch of the epoch ``perm`` exceeds the capacity in primal nodes, primal edges (= dual nodes) or dual
+        edges: the totals of every batch are taken on the device and read back once."""
+        ds, B = self.primal_ds, self.batch_size
+        p = torch.as_tensor(perm).to(ds.x_all.device, torch.int64).reshape(-1)
+        full = int(p.numel()) // B
+        if full == 0:
+            return
+        p = p[: full * B].view(full, B)
+        n, e, ed = torch.stack([ds.node_counts[p].sum(1).max(), ds.edge_counts[p].sum(1).max(),
+                                self.dual_ds.edge_counts[p].sum(1).max()]).tolist()
+        if n + 2 > self.capacity[0] or e > self.capacity[1] or ed > self.capacity[2]:
+            raise ValueError(f"a batch of this epoch needs (N, E, E_dual) = ({n} + 2 padding nodes, {e}, {ed}), above the capacity "
+                             f"{self.capacity}")

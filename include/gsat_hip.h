@@ -581,6 +581,22 @@ int gsat_info_loss_valid_fwd(const float* att, const float* r_vec, float r_scala
 int gsat_info_loss_valid_bwd(const float* att, const float* r_vec, float r_scalar, const float* r_dev, const float* gout,
                              int64_t M, const int32_t* m_valid_dev, float* datt, void* stream);
 
+/*
+ * Soft-F1 sparsity loss over the first m entries: loss[0] = (1 - f1) + sum|p| / max(m, 1) with TP = sum p*y, P = sum p, G = sum y,
+ * precision = TP / (P + 1e-6), recall = TP / (G + 1e-6), f1 = 2 precision recall / (precision + recall + 1e-6).
+ * replaces: src/run_gsat.py:151-180.  m = *m_valid_dev (int32 on the device, clamped to [0, M]) or M when m_valid_dev is NULL; entries at
+ * or beyond m are not read.  partial: scratch float[1024], 16-byte aligned.  stats float[8] = (TP, P, G, sum|p|, dloss/dTP, dloss/dP,
+ * 1 / max(m, 1), 0) feeds the backward: dp[k] = gout[0] * (stats[4] y[k] + stats[5] + sign(p[k]) stats[6]) for k < m and exactly 0
+ * beyond (y is a label: no gradient).  Two-stage sums in a fixed order, no atomics: equal inputs give equal bits.  One block of the
+ * first stage covers gsat_f1_sparsity_block_entries() entries until gsat_f1_sparsity_max_blocks() blocks are in use.
+ */
+int gsat_f1_sparsity_fwd(const float* p, const float* y, int64_t M, const int32_t* m_valid_dev, float* partial, float* loss,
+                         float* stats, void* stream);
+int gsat_f1_sparsity_bwd(const float* p, const float* y, const float* stats, const float* gout, int64_t M,
+                         const int32_t* m_valid_dev, float* dp, void* stream);
+int64_t gsat_f1_sparsity_block_entries(void);
+int64_t gsat_f1_sparsity_max_blocks(void);
+
 /* out[i] = (int32) in[i] */
 int gsat_narrow_i64(const int64_t* in, int64_t n, int32_t* out, void* stream);
 
