@@ -1,0 +1,199 @@
+"""A device-resident log of one evaluation epoch, scored once at its end.
+
+The meters of :mod:`dp_gsat_amd.explain` / :mod:`dp_gsat_amd.evaluate` keep Python lists of cloned tensors and launch their ranking
+and delta-KL kernels batch by batch: neither survives a captured hipGraph, whose every replay would write to the same addresses.
+:class:`EpochLog` allocates everything once and ``append`` is two launches of csrc/eval_log.hip that find their offsets in a counter
+block ON THE DEVICE, so an evaluation batch -- collation, forward, append -- replays as one graph (``ReplayedEval``).  The log is itself
+one big collated batch whose edges already lie graph by graph: ``compute`` ranks all its graphs in one ``gsat_rank_edges`` call with
+the identity as edge order, and scores the rest with the kernels the meters use plus the per-segment delta-KL.
+
+Layout after the appends (prefix lengths in ``state`` = edges, graphs, batches, flags):
+  att fp32[edges], label uint8[edges]      attention / 0-1 label, graph by graph; inside a graph by ascending edge id of its batch
+  graph_edge_ptr int32[graphs + 1]          first edge of every logged graph
+  logits fp32[graphs, logit_cols], y fp32[graphs, y_cols]      (NaN = unlabelled)
+  batch_edge_ptr int64[batches + 1]         first edge of every logged batch
+  loss_sums float64[3]                      sums of the (loss, pred, info) triples; NaN once a batch came without one
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from ._lib import GsatHipError, call, ptr, stream
+from .evaluate import MAX_BINS, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve
+from .explain import _att, _labels, attention_auroc, delta_kl_stats, rank_edges_lds_cap
+from .graph_index import call_size, get_index
+
+FLAG_OVERFLOW, FLAG_FULL = 1, 2
+
+
+def delta_kl_segments_chunk() -> int:
+    """Entries of a segment that one workgroup of ``gsat_delta_kl_segments`` handles; longer segments are cut into chunks of it."""
+    return call_size("gsat_delta_kl_segments_chunk")
+
+
+def delta_kl_segments(att, exp_labels, seg_ptr, max_seg_len: Optional[int] = None, eps: float = 1e-6) -> torch.Tensor:
+    """float32[S, 3] on the device: row s = ``delta_kl_stats(att[seg_ptr[s]:seg_ptr[s+1]], exp_labels[...])``, every segment with its own
+    r.  ``seg_ptr``: int64[S + 1] on the device.  ``max_seg_len``: a bound on the longest segment when the host knows one (it sizes the
+    grid; default: all of ``att``); a longer segment gives a NaN row.  Bitwise repeatable."""
+    a = _att(att)
+    E = a.shape[0]
+    lab = _labels(exp_labels, E)
+    if not isinstance(seg_ptr, torch.Tensor) or not seg_ptr.is_cuda:
+        raise GsatHipError("dp_gsat_amd.eval_log needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    if seg_ptr.dtype != torch.int64 or seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+        raise ValueError("seg_ptr must be an int64 vector of S + 1 entries")
+    sp = seg_ptr.contiguous()
+    S = int(sp.shape[0]) - 1
+    out = torch.empty((S, 3), dtype=torch.float32, device=a.device)
+    if S == 0:
+        return out
+    bound = E if max_seg_len is None else min(max(int(max_seg_len), 0), E)
+    ws_bytes = call_size("gsat_delta_kl_segments_workspace_bytes", S, bound)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    call("gsat_delta_kl_segments", ptr(a) if E else None, ptr(lab) if E else None, ptr(sp), S, E, bound, float(eps), ptr(out), ptr(ws),
+         ws_bytes, stream())
+    return out
+
+
+class EpochLog:
+    """``EpochLog(k, max_graphs, max_edges, max_batches, logit_cols, y_cols=1, bins=64, multi_label=False, device=None)``: the arrays of the
+    module docstring, allocated once (plain attributes: their addresses never change).  ``append`` issues kernels only; ``compute`` reads
+    the device twice.  An append that cannot be taken -- a padded batch whose overflow word is set (flag bit 0), or one that would
+    exceed ``max_edges``, ``max_graphs`` or ``max_batches`` (flag bit 1) -- writes nothing and is reported by ``compute``."""
+
+    def __init__(self, k: int, max_graphs: int, max_edges: int, max_batches: int, logit_cols: int, y_cols: int = 1, bins: int = 64,
+                 multi_label: bool = False, device=None):
+        if int(k) <= 0:
+            raise ValueError("k must be positive")
+        if not 1 <= int(bins) <= MAX_BINS:
+            raise ValueError(f"need 1 <= bins <= {MAX_BINS}")
+        if min(int(max_graphs), int(max_edges), int(max_batches)) < 0 or int(logit_cols) < 1 or int(y_cols) < 1:
+            raise ValueError("EpochLog needs non-negative capacities and at least one logit and one label column")
+        if int(max_edges) >= 2 ** 31 or int(max_graphs) >= 2 ** 31:
+            raise ValueError("EpochLog: max_edges and max_graphs must be below 2**31 (the ranking kernels carry int32 edge ids)")
+        self.k, self.bins, self.multi_label = int(k), int(bins), bool(multi_label)
+        self.max_graphs, self.max_edges, self.max_batches = int(max_graphs), int(max_edges), int(max_batches)
+        self.logit_cols, self.y_cols = int(logit_cols), int(y_cols)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise GsatHipError("dp_gsat_amd.eval_log needs a ROCm (cuda) device: the HIP path has no CPU fallback")
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        self.att, self.label = new(self.max_edges, torch.float32), new(self.max_edges, torch.uint8)
+        self.graph_edge_ptr = new(self.max_graphs + 1, torch.int32)
+        self.logits, self.y = new((self.max_graphs, self.logit_cols), torch.float32), new((self.max_graphs, self.y_cols), torch.float32)
+        self.batch_edge_ptr = new(self.max_batches + 1, torch.int64)
+        self.loss_sums = torch.zeros(3, dtype=torch.float64, device=dev)
+        self.state = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._graph_ids = torch.arange(self.max_graphs, dtype=torch.int64, device=dev)
+        self._batch_ids = torch.arange(self.max_batches, dtype=torch.int64, device=dev)
+
+    def reset(self) -> None:
+        """Empty the log: ``state`` and ``loss_sums`` are zeroed on the device, nothing is read."""
+        self.state.zero_()
+        self.loss_sums.zero_()
+
+    def append(self, att, data, clf_logits, losses=None) -> None:
+        """Log one batch.  ``data``: a collated batch with ``edge_index``, ``batch``, ``edge_label``, ``y`` and ``num_graphs``; for a
+        ``PaddedBatch`` the real graphs and edges are counted by ``data.valid`` on the device, and ``att`` / ``clf_logits`` have capacity
+        shape.  ``losses``: a device float32[3] (loss, pred, info), or None.  Never reads back (given ``data.num_graphs``)."""
+        a = _att(att)
+        E_cap, dev = int(a.shape[0]), a.device
+        if getattr(data, "edge_label", None) is None:
+            raise ValueError("EpochLog.append needs data.edge_label")
+        lab = _labels(data.edge_label, E_cap)
+        if not isinstance(clf_logits, torch.Tensor) or not clf_logits.is_cuda or not data.y.is_cuda:
+            raise GsatHipError("dp_gsat_amd.eval_log needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+        seg = get_index(data.edge_index, int(data.batch.shape[0])).graphs(data.batch, getattr(data, "num_graphs", None))
+        if seg.index.E != E_cap:
+            raise ValueError(f"attention has {E_cap} entries for {seg.index.E} edges")
+        G_cap = seg.G
+        if clf_logits.dim() != 2 or tuple(clf_logits.shape) != (G_cap, self.logit_cols):
+            raise ValueError(f"clf_logits must have shape [{G_cap}, {self.logit_cols}], one row per graph of the batch")
+        if data.y.shape[0] != G_cap or data.y.numel() != G_cap * self.y_cols:
+            raise ValueError(f"data.y must have {G_cap} rows of {self.y_cols} labels")
+        logits = clf_logits.detach().to(torch.float32).contiguous()
+        y = data.y.detach().reshape(G_cap, self.y_cols).to(torch.float32).contiguous()
+        valid = getattr(data, "valid", None)
+        if valid is not None and (valid.dtype != torch.int32 or valid.numel() < 4 or not valid.is_cuda):
+            raise ValueError("data.valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+        if losses is not None:
+            if not isinstance(losses, torch.Tensor) or not losses.is_cuda or losses.numel() != 3:
+                raise ValueError("losses must be a ROCm tensor of three entries (loss, pred, info)")
+            losses = losses.detach().reshape(3).to(torch.float32).contiguous()
+        eptr, eorder = seg.edge_segments[:2]
+        some = lambda t: ptr(t) if t.numel() else None
+        call("gsat_eval_log_append", some(a), some(lab), ptr(eptr), some(eorder), some(logits), some(y),
+             ptr(valid.contiguous()) if valid is not None else None, ptr(losses) if losses is not None else None,
+             E_cap, G_cap, self.logit_cols, self.y_cols, some(self.att), some(self.label), ptr(self.graph_edge_ptr), some(self.logits),
+             some(self.y), ptr(self.batch_edge_ptr), ptr(self.loss_sums), ptr(self.state), self.max_edges, self.max_graphs,
+             self.max_batches, stream())
+
+    def _counts(self):
+        """The first host read: ``state`` and, from the same copy, the largest logged graph and the largest logged batch (in edges)."""
+        st = self.state
+        zero = torch.zeros((), dtype=torch.int64, device=st.device)
+        parts = [st]
+        for ptr_arr, ids, count in ((self.graph_edge_ptr, self._graph_ids, st[1]), (self.batch_edge_ptr, self._batch_ids, st[2])):
+            if ids.numel():
+                sizes = (ptr_arr[1:] - ptr_arr[:-1]).to(torch.int64)               # beyond the count: unwritten memory, masked out
+                parts.append(torch.where(ids < count, sizes, zero).max().view(1))
+            else:
+                parts.append(zero.view(1))
+        return torch.cat(parts).tolist()
+
+    def compute(self) -> dict:
+        """Score everything logged since ``reset``: the keys of ``EvaluationMeter.compute()`` with the same meaning -- one global
+        attention ROC-AUC, the mean over all graphs of hits / k, the mean over the batches of the per-batch delta-KL, class means,
+        histograms and PR curve over all edges, accuracy and ROC-AUC over all graphs -- plus ``loss``, ``pred``, ``info``, the means
+        over the batches (NaN when a batch was appended without ``losses``).  Exactly two host reads: the counts, then the packed
+        results.  ValueError when an append was refused, or nothing was appended."""
+        E, Gn, nb, flags, max_graph_edges, max_batch_edges = self._counts()
+        if flags & FLAG_OVERFLOW:
+            raise ValueError("EpochLog: flag bit 0 is set -- a padded batch did not fit its capacity (valid[3]) and was not logged")
+        if flags & FLAG_FULL:
+            raise ValueError("EpochLog: flag bit 1 is set -- an append would have exceeded max_edges, max_graphs or max_batches "
+                             f"({self.max_edges}, {self.max_graphs}, {self.max_batches}) and was not logged")
+        if nb == 0:
+            raise ValueError("EpochLog.compute() before any append()")
+        dev = self.state.device
+        a, lab = self.att[:E], self.label[:E]
+        logits, y = self.logits[:Gn], self.y[:Gn]
+        f64 = lambda v: torch.full((1,), float(v), dtype=torch.float64, device=dev)
+        # precision@k: the log is one collated batch whose edge order is the identity
+        if Gn and E:
+            hits = torch.empty(Gn, dtype=torch.int32, device=dev)
+            identity = torch.arange(E, dtype=torch.int32, device=dev)
+            fused = max_graph_edges <= rank_edges_lds_cap()
+            ws, ws_bytes = None, 0
+            if not fused:
+                ws_bytes = call_size("gsat_rank_edges_workspace_bytes", E)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            call("gsat_rank_edges", ptr(a), ptr(self.graph_edge_ptr), ptr(identity), ptr(lab), E, Gn, self.k, int(max_graph_edges), 0,
+                 None, None, None, ptr(hits), ptr(ws), ws_bytes, stream())
+            prec = (hits.to(torch.float64).mean() / float(self.k)).view(1)
+        else:
+            prec = f64(0.0 if Gn else float("nan"))
+        dkl = delta_kl_segments(a, lab, self.batch_edge_ptr[:nb + 1], max_batch_edges)[:, 0].double().mean().view(1)
+        means = delta_kl_stats(a, lab)[1:].double()
+        hist = attention_histogram(a, lab, bins=self.bins)
+        acc = classifier_accuracy(logits, y, self.multi_label).view(1) if Gn else f64(float("nan"))
+        binary = self.multi_label or self.logit_cols == 1
+        roc = classifier_rocauc(logits, y).view(1) if binary else f64(0.0)
+        pr = pr_curve(hist)
+        names = ("tp", "fp", "tn", "fn")
+        floats = [attention_auroc(a, lab).view(1), prec, dkl, means, acc, roc, self.loss_sums / float(nb), pr["precision"], pr["recall"]]
+        packed = torch.cat([hist.counts.view(-1), hist.outside] + [pr[n] for n in names] +
+                           [t.view(torch.int64) for t in floats]).cpu().numpy()                   # the second host read
+        B = self.bins
+        ints, fl = packed[:6 * B + 2], packed[6 * B + 2:].view(np.float64)
+        res = {"att_auroc": float(fl[0]), f"precision@{self.k}": float(fl[1]), "delta_kl": float(fl[2]),
+               "avg_signal_att_weights": float(fl[3]), "avg_bkg_att_weights": float(fl[4]), "clf_acc": float(fl[5]), "clf_roc": float(fl[6]),
+               "loss": float(fl[7]), "pred": float(fl[8]), "info": float(fl[9]),
+               "bkg_att_hist": ints[:B].copy(), "signal_att_hist": ints[B:2 * B].copy(), "att_outside": ints[2 * B:2 * B + 2].copy()}
+        curve = {n: ints[2 * B + 2 + i * B:2 * B + 2 + (i + 1) * B].copy() for i, n in enumerate(names)}
+        curve.update(precision=fl[10:10 + B].copy(), recall=fl[10 + B:10 + 2 * B].copy())
+        res["pr_curve"] = curve
+        return res

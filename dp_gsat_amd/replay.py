@@ -10,6 +10,7 @@ from typing import Optional
 
 import torch
 
+from .eval_log import EpochLog
 from .graph_index import clear_cache, set_sync_free, sync_free
 from .gsat import get_r
 from .ops import edge_tensor
@@ -137,6 +138,136 @@ class ReplayedStep:
         n, e = torch.stack([ds.node_counts[p].sum(1).max(), ds.edge_counts[p].sum(1).max()]).tolist()
         if n + 2 > self.capacity[0] or e > self.capacity[1]:
             raise ValueError(f"a batch of this epoch needs (N, E) = ({n} + 2 padding nodes, {e}), above the capacity {self.capacity}")
+
+
+class ReplayedEval:
+    """``ReplayedEval(gsat, dataset, batch_size, k, capacity=None, bins=64, max_graphs=None, max_edges=None)``: an evaluation epoch over
+    ``dataset`` (a PackedDataset with ``edge_label_all``) as replays of ONE captured hipGraph that holds clear_cache, collate_padded,
+    ``gsat.forward_pass(b, 0, False)`` under ``torch.no_grad()`` with every module in ``eval()`` mode, and ``log.append`` into an
+    :class:`~dp_gsat_amd.eval_log.EpochLog` (``log``).  Three warm-up runs on a side stream precede the capture; the modules' training
+    flags, ``sync_free`` and ``sync_loss_dict`` are put back afterwards and the log is reset.  No optimizer is needed.
+
+    The graph reads the parameters and the BatchNorm running statistics where they live, so a replay after ``ReplayedStep.step`` (or an
+    eager optimizer step) scores the new weights.  It writes none of them, draws no noise and no dropout mask, and leaves the device seed
+    stream alone: evaluating between training steps does not change the training run.
+
+    ``max_graphs`` / ``max_edges`` (the log's capacities) default to the dataset's totals; a batch that does not fit ``capacity``, or an
+    append that does not fit the log, is refused on the device and raised by ``run`` / ``log.compute()``.
+
+    Refused with ValueError, like the padded path: the multi-label criterion, ``sync_group`` BatchNorm, and ``DualGSAT``."""
+
+    def __init__(self, gsat, dataset, batch_size: int, k: int, capacity: Optional[tuple] = None, bins: int = 64,
+                 max_graphs: Optional[int] = None, max_edges: Optional[int] = None, graph=None):
+        if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
+            raise ValueError("ReplayedEval replays GSAT.forward_pass; the dual/primal evaluation (DualGSAT) is not covered")
+        if getattr(gsat.criterion, "multi_label", False):
+            raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
+        if any(getattr(m, "sync_group", None) for m in gsat.modules()):
+            raise ValueError("a padded batch cannot take sync_group BatchNorm (its statistics are reduced over ranks on the host's schedule)")
+        if dataset.edge_label_all is None or dataset.y_all is None:
+            raise ValueError("ReplayedEval needs a dataset with edge labels and graph labels")
+        self.gsat, self.dataset, self.batch_size = gsat, dataset, int(batch_size)
+        if not 1 <= self.batch_size <= dataset.num_graphs:
+            raise ValueError("batch_size must be between 1 and the dataset's graph count")
+        self.capacity = tuple(int(c) for c in capacity) if capacity is not None else dataset.capacity_for(self.batch_size)
+        dev = dataset.x_all.device
+        self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
+        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
+        self.batch = self.clf_logits = self.edge_att = self.losses = None
+        self.graph = graph if graph is not None else torch.cuda.CUDAGraph()
+        self._capture(int(k), int(bins), max_graphs, max_edges)
+
+    _r_of = ReplayedStep._r_of
+
+    def _forward(self, b, epoch):
+        """Append the eval-mode forward of batch ``b`` to the log; the modules are in eval mode and sync_loss_dict is off."""
+        with torch.no_grad():
+            att, _, ld, logits = self.gsat.forward_pass(b, epoch, False)
+            losses = torch.stack([ld["loss"].reshape(()), ld["pred"].reshape(()), ld["info"].reshape(())]).to(torch.float32)
+            att = edge_tensor(att)
+            self.log.append(att, b, logits, losses)
+        return att, logits, losses
+
+    def run_once(self):
+        """The body of the captured graph, run on the current stream."""
+        clear_cache()
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity)
+        b.r = self.r
+        self.edge_att, self.clf_logits, self.losses = self._forward(b, 0)
+        self.batch = b
+
+    def _eval_mode(self):
+        """Switch every module to eval mode and sync_loss_dict off; returns what puts both back."""
+        gsat = self.gsat
+        modes = [(m, m.training) for m in gsat.modules()]
+        was_loss_dict = gsat.sync_loss_dict
+        gsat.eval()
+        gsat.sync_loss_dict = False
+
+        def restore():
+            for m, t in modes:
+                m.training = t
+            gsat.sync_loss_dict = was_loss_dict
+        return restore
+
+    def _capture(self, k, bins, max_graphs, max_edges):
+        gsat, ds, dev = self.gsat, self.dataset, self.dataset.x_all.device
+        was_sync_free = sync_free()
+        restore = self._eval_mode()
+        set_sync_free(True)
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                b = ds.collate_padded(self.graph_ids, self.capacity)
+                with torch.no_grad():
+                    logit_cols = int(gsat.forward_pass(b, 0, False)[3].shape[1])
+                y_cols = int(ds.y_all.numel() // max(int(ds.y_all.shape[0]), 1))
+                mg = ds.num_graphs if max_graphs is None else int(max_graphs)
+                me = int(ds.edge_local_all.shape[1]) if max_edges is None else int(max_edges)
+                self.log = EpochLog(k, mg, me, max(-(-mg // self.batch_size), 1), logit_cols, y_cols, bins, False, dev)
+                for _ in range(3):
+                    self.run_once()
+            torch.cuda.current_stream().wait_stream(side)
+            if int(self.batch.valid[3]) != 0:
+                raise ValueError(f"ReplayedEval: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
+            self.log.reset()
+            with torch.cuda.graph(self.graph):
+                self.run_once()
+        finally:
+            set_sync_free(was_sync_free)
+            restore()
+            clear_cache()
+            if getattr(self, "log", None) is not None:
+                self.log.reset()
+
+    def step(self, graph_ids, epoch: int) -> None:
+        """Evaluate the graphs ``graph_ids`` (exactly ``batch_size`` ids) with r = get_r(epoch) and append them to ``log``; nothing is read
+        back.  ``edge_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3] and ``batch`` hold the replay's outputs until the next."""
+        ids = torch.as_tensor(graph_ids)
+        if ids.numel() != self.batch_size:
+            raise ValueError(f"ReplayedEval was captured for {self.batch_size} graphs per step, got {ids.numel()}")
+        self.graph_ids.copy_(ids.reshape(-1), non_blocking=True)
+        self.r.fill_(float(self._r_of(epoch)))
+        self.graph.replay()
+
+    def run(self, graph_ids, epoch: int) -> dict:
+        """One evaluation epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, the
+        tail of fewer than ``batch_size`` graphs runs eagerly (``dataset.collate``, the same eval-mode forward, the same append), and
+        ``log.compute()`` -- two host reads -- gives the scores."""
+        ids = torch.as_tensor(graph_ids).reshape(-1)
+        B, n = self.batch_size, int(ids.numel())
+        self.log.reset()
+        for s in range(0, n - B + 1, B):
+            self.step(ids[s:s + B], epoch)
+        if n % B:
+            restore = self._eval_mode()
+            try:
+                tail = ids[n - n % B:].to(self.dataset.x_all.device, torch.int64)
+                self._forward(self.dataset.collate(tail), epoch)
+            finally:
+                restore()
+        return self.log.compute()
 
 
 class ReplayedDualStep:

@@ -12,6 +12,8 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
 
   * dp_gsat_amd.ReplayedStep (``--graph``, single process) -- every full batch is collated to a fixed capacity and trained by replaying
     ONE captured hipGraph (collation, forward, backward, fused Adam); the tail batch of an epoch runs eagerly.
+  * dp_gsat_amd.ReplayedEval (``--graph``) -- the periodic test evaluation replays a second captured graph (collation, eval-mode forward,
+    append to a device log) batch by batch and scores the log once: two host reads per evaluation.
 
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
@@ -110,9 +112,15 @@ def main():
                                  G.precision_at_k(att, b.edge_label, 5, b.batch, b.edge_index, b.num_graphs).double().mean()]).tolist()
         return acc, auc, prec
 
-    replayed = None
+    replayed = replayed_eval = None
     if args.graph and n_train >= args.batch_size:
         replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
+    if args.graph:
+        replayed_eval = G.ReplayedEval(gsat, ds, min(args.batch_size, len(graphs)), 5)
+
+    def evaluate_replayed(ids, epoch):
+        res = replayed_eval.run(ids, epoch)                       # full batches: replays; the tail: eager; one scoring pass at the end
+        return res["clf_acc"], res["att_auroc"], res["precision@5"]
 
     gen = np.random.RandomState(args.seed)                        # identical permutations on every rank
     for epoch in range(args.epochs):
@@ -139,7 +147,8 @@ def main():
             opt.step()
             tot, nb = tot + ld["loss"], nb + 1
         if rank == 0 and (epoch % 5 == 4 or epoch == args.epochs - 1):
-            acc, auc, prec = evaluate(np.arange(n_train, len(graphs)))
+            test_ids = np.arange(n_train, len(graphs))
+            acc, auc, prec = evaluate_replayed(test_ids, epoch) if replayed_eval is not None else evaluate(test_ids)
             print(f"epoch {epoch + 1:3d}  train loss {float(tot) / nb:.4f}  test acc {acc:.3f}  attention ROC-AUC vs motif edges {auc:.3f}  prec@5 {prec:.3f}",
                   flush=True)
     if world > 1:

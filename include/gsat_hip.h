@@ -797,6 +797,50 @@ int gsat_subgraph_index(const int64_t* edge_index, int64_t num_edges, int64_t nu
  */
 int gsat_gather_rows(const void* table, const int64_t* index, int64_t n, int64_t row_bytes, void* out, void* stream);
 
+/* ================================= evaluation epoch log ===================================== */
+
+/*
+ * Appends one batch to a device-resident log of an evaluation epoch, at the offsets held in log_state int64[4] = (edges logged,
+ * graphs logged, batches logged, flags) ON THE DEVICE; nothing is read back and the launch geometry depends on the capacities only
+ * (capturable, kernels only).
+ * The batch: att fp32[edge_cap] and label uint8[edge_cap] by edge id; edge_ptr int32[graph_cap + 1] / edge_order int32[edge_cap], the
+ * edges grouped by graph with ascending edge ids inside a graph (gsat_build_csr over the edges' graph ids); logits
+ * fp32[graph_cap, logit_cols] and y fp32[graph_cap, y_cols] (NaN = unlabelled, kept); valid int32[4] = (N_real, E_real, B, overflow)
+ * of gsat_collate_padded, nullable: without it all graph_cap graphs are logged, with it the first B; losses fp32[3], nullable.
+ * With G graphs and E = edge_ptr[G] edges to log and (e0, g0, b0) the counts in log_state:
+ *   log_att[e0 + i], log_label[e0 + i] (0 / 1)   = att / label of edge edge_order[i], i < E
+ *   log_graph_edge_ptr[g0 + g]                   = e0 + edge_ptr[g], 0 <= g <= G (entry g0 is only written when g0 == 0)
+ *   log_logits / log_y rows g0 .. g0 + G - 1     = the first G rows
+ *   log_batch_edge_ptr[b0 + 1] = e0 + E          (entry 0 = 0 is written by the first append)
+ *   log_loss_sums double[3]                      += losses, or turn NaN when losses is null
+ * and then log_state = (e0 + E, g0 + G, b0 + 1, flags) by a second launch that the stream orders after the copies, so entries below
+ * the counts never change again.  A batch whose valid[3] is set appends nothing and sets flag bit 0; a batch that would exceed max_edges,
+ * max_graphs or max_batches (or whose counts are not within its own capacities) appends nothing and sets flag bit 1.  Nothing is ever
+ * written beyond the max_* entries.  Destination offsets are arbitrary: every store has element width.  max_edges < 2^31
+ * (GSAT_ERR_UNSUPPORTED otherwise).
+ * replaces: the host lists all_exp_labels / all_att / all_clf_labels / all_clf_logits of dual_run_one_epoch (src/run_gsat.py:646-668).
+ */
+int gsat_eval_log_append(const float* att, const uint8_t* label, const int32_t* edge_ptr, const int32_t* edge_order, const float* logits,
+                         const float* y, const int32_t* valid, const float* losses, int64_t edge_cap, int64_t graph_cap,
+                         int64_t logit_cols, int64_t y_cols, float* log_att, uint8_t* log_label, int32_t* log_graph_edge_ptr,
+                         float* log_logits, float* log_y, int64_t* log_batch_edge_ptr, double* log_loss_sums, int64_t* log_state,
+                         int64_t max_edges, int64_t max_graphs, int64_t max_batches, void* stream);
+
+/*
+ * out fp32[S,3]: row s is the gsat_delta_kl triple of att[seg_ptr[s] : seg_ptr[s+1]] (seg_ptr int64[S+1], non-decreasing, inside
+ * [0, num_edges]); every segment has its own r = clamp(mean(clamp(a))).  An empty segment gives (0, 0, 0) like gsat_delta_kl for E = 0.
+ * max_seg_len bounds the longest segment (num_edges always does); a segment above it, or bounds that are out of order, give a NaN
+ * row -- never a partial evaluation.  A segment is cut into chunks of gsat_delta_kl_segments_chunk() entries, one workgroup per chunk of
+ * one segment (grid: chunks of max_seg_len x S); chunk sums are added in index order, in fp64, without float atomics: bitwise
+ * repeatable, and within summation-order rounding of gsat_delta_kl on the segment alone.  S = 0 is a no-op.  S <= 65535.
+ * workspace: gsat_delta_kl_segments_workspace_bytes(S, max_seg_len).  Kernels only, capturable.
+ * replaces: the per-batch get_delta_kl of dual_run_one_epoch (src/run_gsat.py:664), for all batches of an epoch at once.
+ */
+int64_t gsat_delta_kl_segments_chunk(void);
+size_t gsat_delta_kl_segments_workspace_bytes(int64_t num_segments, int64_t max_seg_len);
+int gsat_delta_kl_segments(const float* att, const uint8_t* label, const int64_t* seg_ptr, int64_t num_segments, int64_t num_edges,
+                           int64_t max_seg_len, double eps, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
