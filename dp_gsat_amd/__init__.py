@@ -14,7 +14,7 @@ from .gsat import (GSAT, ExtractorMLP, concrete_sample, get_r, gumbel_sigmoid, i
                    lift_node_att_to_edge_att, symmetrise_edge_att)
 from .collate import PackedDataset, PaddedBatch, collate_padded_pair, line_graph, line_graph_undirected
 from .padding import current_padding, padded
-from .replay import ReplayedDualStep, ReplayedEval, ReplayedStep
+from .replay import ReplayedDualEval, ReplayedDualStep, ReplayedEval, ReplayedStep
 from .dual_gsat import DualGSAT, f1_sparsity_loss, f1_sparsity_loss_valid
 from .graph_index import BatchIndex, clear_cache, get_index, set_strict, set_sync_free
 from .utils import process_data, reorder_like, set_seed
@@ -32,4 +32,5 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "SubgraphBatch", "edge_subgraph", "node_subgraph", "explanation_subgraph", "explanation_fidelity", "gather_rows",
            "AttentionHistogram", "EvaluationMeter", "attention_histogram", "classifier_accuracy", "classifier_rocauc", "pr_curve",
            "task_auroc_counts", "PaddedBatch", "padded", "current_padding", "ReplayedStep",
-           "ReplayedDualStep", "collate_padded_pair", "f1_sparsity_loss_valid", "EpochLog", "delta_kl_segments", "ReplayedEval"]
+           "ReplayedDualStep", "collate_padded_pair", "f1_sparsity_loss_valid", "EpochLog", "delta_kl_segments", "ReplayedEval",
+           "ReplayedDualEval"]

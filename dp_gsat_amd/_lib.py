@@ -82,6 +82,8 @@ SIGNATURES = {
     "gsat_philox_noise": (INT, [U64, I64, P, P]),
     "gsat_sample_fwd": (INT, [P, P, INT, F32, F32, I64, P, P]),
     "gsat_sample_bwd": (INT, [P, P, F32, I64, P, P]),
+    "gsat_gumbel_sigmoid_philox": (INT, [P, I64, F32, F32, U64, P, P, P]),
+    "gsat_philox_gumbel_noise": (INT, [U64, I64, P, P]),
     "gsat_lift_fwd": (INT, [P, P, P, I64, P, P]),
     "gsat_lift_bwd": (INT, [P, P, P, P, P, P, P, P, I64, P, P]),
     "gsat_symmetrise": (INT, [P, P, P, I64, P, P]),

@@ -25,6 +25,50 @@ __global__ void k_sample_bwd(const float* __restrict__ att, const float* __restr
     dz[m] = datt[m] * a * (1.f - a) / temp;
 }
 
+// Gumbel-sigmoid whose uniform is drawn here: rows 4q .. 4q+3 take the words x, y, z, w of ONE Philox call (stream 5, counter q), mapped
+// to [0, 1) at 24 bits like torch.rand.  gumbel_uniform4 is shared with the reporter kernel, so the two cannot drift apart.
+__device__ __forceinline__ float4 gumbel_uniform4(uint64_t seed, int64_t q) {
+    const uint4 r = philox4x32(seed, (uint32_t)q, 0u, 5u, 0x5A17u);
+    const float k = 1.0f / 16777216.0f;
+    return make_float4((float)(r.x >> 8) * k, (float)(r.y >> 8) * k, (float)(r.z >> 8) * k, (float)(r.w >> 8) * k);
+}
+
+// the expression of k_sample_fwd mode 2, operation for operation (the results are compared bitwise)
+__device__ __forceinline__ float gumbel_sigmoid1(float z, float u, float temp, float eps) {
+    float t = z;
+    t += -logf(-logf(u + eps) + eps);
+    return 1.f / (1.f + expf(-t / temp));
+}
+
+// four entries per thread; VEC (z and att 16-byte aligned): one 16-byte load and store when all four are in range
+template <bool VEC>
+__global__ __launch_bounds__(EB) void k_gumbel_sigmoid_philox(const float* __restrict__ z, int64_t M, float temp, float eps, SeedRef seed,
+                                                              float* __restrict__ att) {
+    const int64_t q = (int64_t)blockIdx.x * EB + threadIdx.x, m = 4 * q;
+    if (m >= M) return;
+    const float4 u = gumbel_uniform4(seed.get(), q);
+    if (VEC && m + 4 <= M) {
+        const float4 a = ld4(z + m);
+        st4(att + m, make_float4(gumbel_sigmoid1(a.x, u.x, temp, eps), gumbel_sigmoid1(a.y, u.y, temp, eps),
+                                 gumbel_sigmoid1(a.z, u.z, temp, eps), gumbel_sigmoid1(a.w, u.w, temp, eps)));
+    } else {
+        att[m] = gumbel_sigmoid1(z[m], u.x, temp, eps);
+        if (m + 1 < M) att[m + 1] = gumbel_sigmoid1(z[m + 1], u.y, temp, eps);
+        if (m + 2 < M) att[m + 2] = gumbel_sigmoid1(z[m + 2], u.z, temp, eps);
+        if (m + 3 < M) att[m + 3] = gumbel_sigmoid1(z[m + 3], u.w, temp, eps);
+    }
+}
+
+__global__ __launch_bounds__(EB) void k_philox_gumbel_noise(uint64_t seed, int64_t M, float* __restrict__ U) {
+    const int64_t q = (int64_t)blockIdx.x * EB + threadIdx.x, m = 4 * q;
+    if (m >= M) return;
+    const float4 u = gumbel_uniform4(seed, q);
+    U[m] = u.x;
+    if (m + 1 < M) U[m + 1] = u.y;
+    if (m + 2 < M) U[m + 2] = u.z;
+    if (m + 3 < M) U[m + 3] = u.w;
+}
+
 __global__ void k_lift_fwd(const float* __restrict__ a, const int32_t* __restrict__ src, const int32_t* __restrict__ dst, int64_t E,
                            float* __restrict__ out) {
     int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -139,6 +183,29 @@ int gsat_sample_bwd(const float* att, const float* datt, float temp, int64_t M, 
     if (M == 0) return GSAT_OK;
     GSAT_REQUIRE(att && datt && dlogits, GSAT_ERR_ARG, "gsat_sample_bwd: null pointer");
     k_sample_bwd<<<GRID1(M)>>>(att, datt, temp, M, dlogits);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_gumbel_sigmoid_philox(const float* logits, int64_t M, float tau, float eps, uint64_t seed, const uint64_t* seed_dev, float* att,
+                               void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(M >= 0 && M < (1ll << 31) && tau > 0.f, GSAT_ERR_ARG, "gsat_gumbel_sigmoid_philox: bad argument");
+    if (M == 0) return GSAT_OK;
+    GSAT_REQUIRE(logits && att, GSAT_ERR_ARG, "gsat_gumbel_sigmoid_philox: null pointer");
+    const SeedRef ref{seed, seed_dev};
+    if ((((uintptr_t)logits | (uintptr_t)att) & 15) == 0) k_gumbel_sigmoid_philox<true><<<GRID1(ceil_div(M, 4))>>>(logits, M, tau, eps, ref, att);
+    else k_gumbel_sigmoid_philox<false><<<GRID1(ceil_div(M, 4))>>>(logits, M, tau, eps, ref, att);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_philox_gumbel_noise(uint64_t seed, int64_t M, float* U, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(M >= 0 && M < (1ll << 31), GSAT_ERR_ARG, "gsat_philox_gumbel_noise: bad M");
+    if (M == 0) return GSAT_OK;
+    GSAT_REQUIRE(U, GSAT_ERR_ARG, "gsat_philox_gumbel_noise: null pointer");
+    k_philox_gumbel_noise<<<GRID1(ceil_div(M, 4))>>>(seed, M, U);
     GSAT_LAUNCH_CHECK();
     return GSAT_OK;
 }

@@ -67,6 +67,7 @@ class DualGSAT(nn.Module):
         self.mix_alpha, self.mix_after_epoch = mix_alpha, mix_after_epoch
         self.gumbel_tau, self.gumbel_noise_in_eval = gumbel_tau, gumbel_noise_in_eval
         self.sync_loss_dict = True
+        self.keep_dual_att, self.dual_att = False, None      # ReplayedDualEval: keep the (detached) dual node attention of the last forward
 
     # -- src/run_gsat.py:121-149 -----------------------------------------------------------------------------------
     def __loss__(self, primal_att, dual_att, primal_clf_logits, dual_clf_logits, primal_clf_labels, dual_clf_labels,
@@ -97,13 +98,16 @@ class DualGSAT(nn.Module):
 
     # -- src/run_gsat.py:189-428 -----------------------------------------------------------------------------------
     def dual_forward_pass(self, primal_data, dual_data, epoch, training, primal_noise=None, dual_noise=None,
-                          primal_masks=None, dual_masks=None):
+                          primal_masks=None, dual_masks=None, dual_seed=None):
+        """``dual_seed`` (an int, or a 1-element int64 ROCm tensor): where the dual Gumbel noise is drawn and ``dual_noise`` is None, draw
+        it inside the sampler kernel from this seed (``gumbel_sigmoid(seed=)``) instead of from torch's generator."""
         from .graph_index import get_index
         if getattr(primal_data, "valid", None) is not None or getattr(dual_data, "valid", None) is not None:
             if getattr(primal_data, "pair", None) is not dual_data or getattr(dual_data, "pair", None) is not primal_data:
                 raise ValueError("DualGSAT takes padded batches only as a pair from collate_padded_pair (whose primal edge slots and dual "
                                  "node rows line up): use it, or collate")
-            return self._pair_forward_pass(primal_data, dual_data, epoch, training, primal_noise, dual_noise, primal_masks, dual_masks)
+            return self._pair_forward_pass(primal_data, dual_data, epoch, training, primal_noise, dual_noise, primal_masks, dual_masks,
+                                           dual_seed)
         for d in (primal_data, dual_data):
             if getattr(d, "num_graphs", None) is not None:      # prime the segment cache without `batch.max()` (a host sync)
                 get_index(d.edge_index, d.x.shape[0]).graphs(d.batch, int(d.num_graphs))
@@ -117,9 +121,11 @@ class DualGSAT(nn.Module):
         dual_emb = self.dual_clf.get_emb(dual_data.x, dual_data.edge_index, batch=dual_data.batch, edge_attr=dual_data.edge_attr)
         dual_att_log_logits = self.dual_extractor(dual_emb, dual_data.edge_index, dual_data.batch, dropout_masks=dual_masks)
         if training or self.gumbel_noise_in_eval:
-            dual_node_att = gumbel_sigmoid(dual_att_log_logits, tau=self.gumbel_tau, noise=dual_noise)       # :222
+            dual_node_att = gumbel_sigmoid(dual_att_log_logits, tau=self.gumbel_tau, noise=dual_noise, seed=dual_seed)       # :222
         else:
             dual_node_att = Sample.apply(dual_att_log_logits, None, 0, self.gumbel_tau, 0.0)   # sigmoid(logits / tau), no noise
+        if self.keep_dual_att:
+            self.dual_att = dual_node_att.detach()
         y_uv = primal_data.edge_label.float().to(dual_node_att.device)
         f1_loss = f1_sparsity_loss(dual_node_att, y_uv)                                                       # :226-227
         dual_edge_att = self._edge_att(dual_node_att, dual_data, self.dual_learn_edge_att)                     # :231-239
@@ -135,7 +141,7 @@ class DualGSAT(nn.Module):
         loss = loss + f1_loss                                                                                 # :281
         return primal_edge_att, loss, loss_dict, primal_clf_logits
 
-    def _pair_forward_pass(self, pb, db, epoch, training, primal_noise, dual_noise, primal_masks, dual_masks):
+    def _pair_forward_pass(self, pb, db, epoch, training, primal_noise, dual_noise, primal_masks, dual_masks, dual_seed=None):
         """``dual_forward_pass`` on a padded pair (collate_padded_pair): dual node row k < Ep is primal edge slot k.  Every primal module runs
         inside ``padded(pb.valid)``, every dual one inside ``padded(db.valid)``; the whole-batch reductions take their counts from the
         device (f1 and the primal info loss: pb.valid[1]; the dual info loss: db.valid[1], with ``db.r`` -- one device float, when set --
@@ -165,9 +171,11 @@ class DualGSAT(nn.Module):
             dual_emb = self.dual_clf.get_emb(db.x, db.edge_index, batch=db.batch, edge_attr=db.edge_attr)
             dual_att_log_logits = self.dual_extractor(dual_emb, db.edge_index, db.batch, dropout_masks=dual_masks)
         if training or self.gumbel_noise_in_eval:
-            dual_node_att = gumbel_sigmoid(dual_att_log_logits, tau=self.gumbel_tau, noise=dual_noise)
+            dual_node_att = gumbel_sigmoid(dual_att_log_logits, tau=self.gumbel_tau, noise=dual_noise, seed=dual_seed)
         else:
             dual_node_att = Sample.apply(dual_att_log_logits, None, 0, self.gumbel_tau, 0.0)
+        if self.keep_dual_att:
+            self.dual_att = dual_node_att.detach()
         n_edges = pb.valid[1:2]                                                  # = db.valid[0:1]: the real primal edges / dual nodes
         dual_on_edges = dual_node_att[:Ep]
         f1_loss = f1_sparsity_loss_valid(dual_on_edges, pb.edge_label, n_edges)

@@ -14,7 +14,8 @@ import torch.nn as nn
 from .get_model import MLP
 from .graph_index import get_index, sync_free
 from .padding import current_padding, padded
-from .ops import ExtractorAttention, InfoLoss, Lift, LiftedAttention, Sample, Symmetrise, device_seed, edge_tensor, new_seed
+from .ops import (ExtractorAttention, InfoLoss, Lift, LiftedAttention, Sample, SamplePhilox, Symmetrise, device_seed, edge_tensor,
+                  new_seed)
 
 
 class ExtractorMLP(nn.Module):
@@ -101,8 +102,11 @@ def concrete_sample(att_log_logit, temp=1.0, training=True, noise=None):
     return Sample.apply(att_log_logit, None, 0, 1.0, 0.0)
 
 
-def gumbel_sigmoid(logits, tau=1.0, eps=1e-10, noise=None):
-    """src/run_gsat.py:182-187."""
+def gumbel_sigmoid(logits, tau=1.0, eps=1e-10, noise=None, seed=None):
+    """src/run_gsat.py:182-187.  ``noise``: explicit U (parity); else ``seed`` -- an int, or a 1-element int64 ROCm tensor read on the
+    device -- draws U inside the kernel (Philox stream 5, row-keyed: no tensor, no generator); with neither, ``torch.rand_like``."""
+    if noise is None and seed is not None:
+        return SamplePhilox.apply(logits, seed, tau, eps)
     if noise is None:
         noise = torch.rand_like(logits)
     return Sample.apply(logits, noise, 2, tau, eps)

@@ -552,6 +552,35 @@ class Sample(torch.autograd.Function):
         return dz, None, None, None, None
 
 
+class SamplePhilox(torch.autograd.Function):
+    """Gumbel-sigmoid (``Sample`` mode 2) whose uniform is drawn inside the kernel from Philox stream 5 of ``seed``: an int, or a 1-element
+    int64 ROCm tensor that the kernel reads (a captured graph then follows whatever rewrites that word).  No noise tensor exists; the
+    backward is ``Sample``'s."""
+
+    @staticmethod
+    def forward(ctx, logits, seed, temp: float, eps: float):
+        z = _f32c(logits)
+        seed_dev = None
+        if isinstance(seed, torch.Tensor):
+            if seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
+                raise ValueError("seed must be an int or a 1-element int64 ROCm tensor")
+            seed, seed_dev = 0, seed
+        att = torch.empty_like(z)
+        call("gsat_gumbel_sigmoid_philox", ptr(z), z.numel(), float(temp), float(eps), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev),
+             ptr(att), stream())
+        ctx.save_for_backward(att)
+        ctx.temp = float(temp)
+        return att
+
+    @staticmethod
+    def backward(ctx, datt):
+        (att,) = ctx.saved_tensors
+        datt = _f32c(datt)
+        dz = torch.empty_like(att)
+        call("gsat_sample_bwd", ptr(att), ptr(datt), ctx.temp, att.numel(), ptr(dz), stream())
+        return dz, None, None, None
+
+
 class Lift(torch.autograd.Function):
     """edge_att = node_att[src] * node_att[dst]  (example/gsat.py:112-117)."""
 

@@ -16,6 +16,38 @@ from .gsat import get_r
 from .ops import edge_tensor
 
 
+def _eval_mode(model):
+    """Switch every module of ``model`` to eval mode and its sync_loss_dict off; returns what puts both back."""
+    modes = [(m, m.training) for m in model.modules()]
+    was_loss_dict = model.sync_loss_dict
+    model.eval()
+    model.sync_loss_dict = False
+
+    def restore():
+        for m, t in modes:
+            m.training = t
+        model.sync_loss_dict = was_loss_dict
+    return restore
+
+
+def _padded_pair_setup(m, primal_ds, dual_ds, batch_size, capacity):
+    """The refusals of a replayed padded pair (those ``DualGSAT._pair_forward_pass`` makes, before anything is captured); returns
+    (batch_size, capacity) as an int and a triple of ints."""
+    if m.primal_criterion.multi_label or m.dual_criterion.multi_label:
+        raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
+    if m.primal_learn_edge_att or m.dual_learn_edge_att:
+        raise ValueError("a padded pair takes node attention on both sides (the MUTAG configs), not edge attention")
+    primal_ds.check_pair(dual_ds)
+    batch_size = int(batch_size)
+    if not 1 <= batch_size <= primal_ds.num_graphs:
+        raise ValueError("batch_size must be between 1 and the dataset's graph count")
+    cap = capacity if capacity is not None else primal_ds.pair_capacity_for(dual_ds, batch_size)
+    cap = tuple(int(c) for c in cap)
+    if len(cap) != 3:
+        raise ValueError("capacity is (N_cap, E_cap, E_dual_cap)")
+    return batch_size, cap
+
+
 class ReplayedStep:
     """``ReplayedStep(gsat, dataset, batch_size, capacity=None)``: captures clear_cache, collate_padded, forward_pass,
     zero_grad(set_to_none=True), backward and optimizer.step() of ``gsat`` on ``dataset`` (a PackedDataset) once, after three warm-up
@@ -154,12 +186,13 @@ class ReplayedEval:
     ``max_graphs`` / ``max_edges`` (the log's capacities) default to the dataset's totals; a batch that does not fit ``capacity``, or an
     append that does not fit the log, is refused on the device and raised by ``run`` / ``log.compute()``.
 
-    Refused with ValueError, like the padded path: the multi-label criterion, ``sync_group`` BatchNorm, and ``DualGSAT``."""
+    Refused with ValueError, like the padded path: the multi-label criterion, ``sync_group`` BatchNorm, and ``DualGSAT`` (see
+    ``ReplayedDualEval``)."""
 
     def __init__(self, gsat, dataset, batch_size: int, k: int, capacity: Optional[tuple] = None, bins: int = 64,
                  max_graphs: Optional[int] = None, max_edges: Optional[int] = None, graph=None):
         if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
-            raise ValueError("ReplayedEval replays GSAT.forward_pass; the dual/primal evaluation (DualGSAT) is not covered")
+            raise ValueError("ReplayedEval replays GSAT.forward_pass; the dual/primal evaluation (DualGSAT) is ReplayedDualEval's")
         if getattr(gsat.criterion, "multi_label", False):
             raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
         if any(getattr(m, "sync_group", None) for m in gsat.modules()):
@@ -198,17 +231,7 @@ class ReplayedEval:
 
     def _eval_mode(self):
         """Switch every module to eval mode and sync_loss_dict off; returns what puts both back."""
-        gsat = self.gsat
-        modes = [(m, m.training) for m in gsat.modules()]
-        was_loss_dict = gsat.sync_loss_dict
-        gsat.eval()
-        gsat.sync_loss_dict = False
-
-        def restore():
-            for m, t in modes:
-                m.training = t
-            gsat.sync_loss_dict = was_loss_dict
-        return restore
+        return _eval_mode(self.gsat)
 
     def _capture(self, k, bins, max_graphs, max_edges):
         gsat, ds, dev = self.gsat, self.dataset, self.dataset.x_all.device
@@ -297,18 +320,8 @@ class ReplayedDualStep:
         for side, opt in (("primal", m.primal_optimizer), ("dual", m.dual_optimizer)):
             if opt is None or not all(g.get("capturable", False) for g in opt.param_groups):
                 raise ValueError(f"ReplayedDualStep needs a capturable {side} optimizer, e.g. torch.optim.Adam(params, capturable=True, fused=True)")
-        if m.primal_criterion.multi_label or m.dual_criterion.multi_label:
-            raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
-        if m.primal_learn_edge_att or m.dual_learn_edge_att:
-            raise ValueError("a padded pair takes node attention on both sides (the MUTAG configs), not edge attention")
-        primal_ds.check_pair(dual_ds)
-        self.model, self.primal_ds, self.dual_ds, self.batch_size = m, primal_ds, dual_ds, int(batch_size)
-        if not 1 <= self.batch_size <= primal_ds.num_graphs:
-            raise ValueError("batch_size must be between 1 and the dataset's graph count")
-        cap = capacity if capacity is not None else primal_ds.pair_capacity_for(dual_ds, self.batch_size)
-        self.capacity = tuple(int(c) for c in cap)
-        if len(self.capacity) != 3:
-            raise ValueError("capacity is (N_cap, E_cap, E_dual_cap)")
+        self.batch_size, self.capacity = _padded_pair_setup(m, primal_ds, dual_ds, batch_size, capacity)
+        self.model, self.primal_ds, self.dual_ds = m, primal_ds, dual_ds
         dev = primal_ds.x_all.device
         self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
         self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
@@ -443,3 +456,193 @@ class ReplayedDualStep:
         if n + 2 > self.capacity[0] or e > self.capacity[1] or ed > self.capacity[2]:
             raise ValueError(f"a batch of this epoch needs (N, E, E_dual) = ({n} + 2 padding nodes, {e}, {ed}), above the capacity "
                              f"{self.capacity}")
+
+
+# The (base, counter) states of every ReplayedDualEval: a captured graph holds its state's address in a gsat_seed_next node, so a state
+# is written in place and lives as long as the process.
+_EVAL_SEED_STATES = []
+_DUAL_SCORES = ("att_auroc", "precision@{k}", "delta_kl", "avg_signal_att_weights", "avg_bkg_att_weights")
+
+
+class ReplayedDualEval:
+    """``ReplayedDualEval(dual_gsat, primal_ds, dual_ds, batch_size, k, capacity=None, bins=64, max_graphs=None, max_edges=None,
+    score_dual=False, seed=None, graphs=None)``: a dual/primal evaluation epoch (``dual_eval_one_batch`` over a dataset and its dual) as
+    replays of captured hipGraphs.  One replay holds clear_cache, collate_padded_pair, one gsat_seed_next, ``dual_forward_pass(pb, db,
+    epoch, False, dual_seed=word)`` under ``torch.no_grad()`` with every module in ``eval()`` mode, and ``log.append`` of the primal
+    attention, the primal logits and the (loss, pred, info) triple of the returned loss dict into an
+    :class:`~dp_gsat_amd.eval_log.EpochLog` (``log``).  As in ``ReplayedDualStep`` the mix is a host branch: TWO graphs (unmixed, mixed)
+    over the same parameters, and ``step`` / ``run`` pick one by ``epoch > mix_after_epoch``.  Three warm-up runs on a side stream
+    precede the captures; training flags, ``sync_free`` and ``sync_loss_dict`` are put back afterwards and the logs are reset.
+
+    The dual attention is Gumbel-sampled in eval mode too (``gumbel_noise_in_eval``).  Its uniform is drawn inside the sampler kernel
+    (``gumbel_sigmoid(seed=)``) from a seed stream of the evaluator's own: ``seed_state`` = int64[2] (base, counter); ``base`` is ``seed``,
+    or derived from ``torch.initial_seed()`` without drawing from any generator.  ``run(ids, epoch)`` restarts it at ``(base, epoch <<
+    32)``, so batch j of the run uses the word gsat_seed_next gives for the counter ``(epoch << 32) + j`` and an evaluation epoch is a
+    function of the weights, the ids, the epoch and the base alone.  Neither ``device_seed()``'s stream nor torch's CUDA or CPU generator
+    is touched: evaluating between ``ReplayedDualStep`` steps leaves the training run bitwise unchanged.  With
+    ``gumbel_noise_in_eval=False`` nothing is drawn and the counter does not move.
+
+    ``score_dual=True``: a second log, ``dual_log``, takes the same primal batches with the dual attention on the primal edge slots in
+    place of the primal attention (dual node row k is primal edge slot k), and ``run`` adds its attention scores under a ``dual_`` prefix.
+
+    Refused with ValueError before anything is captured: what a padded pair refuses (the multi-label criterion, edge attention,
+    ``check_pair``, a capacity that is no triple), ``sync_group`` BatchNorm, a model without ``dual_forward_pass`` and a dataset without
+    edge labels or graph labels.  Overflow of the joint capacity sets the log's flag bit 0 and is raised by ``run``; ``check_epoch``
+    tells beforehand."""
+
+    def __init__(self, dual_gsat, primal_ds, dual_ds, batch_size: int, k: int, capacity: Optional[tuple] = None, bins: int = 64,
+                 max_graphs: Optional[int] = None, max_edges: Optional[int] = None, score_dual: bool = False, seed: Optional[int] = None,
+                 graphs=None):
+        m = dual_gsat
+        if not hasattr(m, "dual_forward_pass"):
+            raise ValueError("ReplayedDualEval replays DualGSAT.dual_forward_pass; ReplayedEval covers a plain GSAT")
+        if any(getattr(mod, "sync_group", None) for mod in m.modules()):
+            raise ValueError("a padded batch cannot take sync_group BatchNorm (its statistics are reduced over ranks on the host's schedule)")
+        if primal_ds.edge_label_all is None or primal_ds.y_all is None or dual_ds.y_all is None:
+            raise ValueError("ReplayedDualEval needs datasets with edge labels (primal) and graph labels")
+        self.batch_size, self.capacity = _padded_pair_setup(m, primal_ds, dual_ds, batch_size, capacity)
+        self.model, self.primal_ds, self.dual_ds = m, primal_ds, dual_ds
+        dev = primal_ds.x_all.device
+        self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
+        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
+        if seed is None:        # a fixed mix of torch.initial_seed(): follows torch.manual_seed, draws nothing
+            seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & 0x7FFFFFFFFFFFFFFF
+        self.base = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.seed_state = torch.empty(2, dtype=torch.int64, device=dev)
+        _EVAL_SEED_STATES.append(self.seed_state)
+        self._set_seed_state(0)
+        self.score_dual = bool(score_dual)
+        self.log = self.dual_log = None
+        self.batch = self.dual_batch = self.edge_att = self.clf_logits = self.losses = self.dual_att = None
+        unmixed, mixed = graphs if graphs is not None else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
+        self.graphs = {False: unmixed, True: mixed}
+        self._outputs = {}
+        self._capture(int(k), int(bins), max_graphs, max_edges)
+
+    _r_of = ReplayedDualStep._r_of
+    check_epoch = ReplayedDualStep.check_epoch
+
+    def _set_seed_state(self, counter):
+        signed = lambda v: v - (1 << 64) if v >= 1 << 63 else v
+        self.seed_state.copy_(torch.tensor([signed(self.base), signed(int(counter) & 0xFFFFFFFFFFFFFFFF)], dtype=torch.int64))
+
+    def _forward(self, pb, db, epoch):
+        """Append the eval-mode forward of the pair (padded or not) to the log(s), with the stream's next seed word when noise is drawn;
+        the modules are in eval mode and sync_loss_dict is off.  Returns (primal attention, logits, losses, dual attention on the primal
+        edges, seed word)."""
+        from ._lib import call, ptr, stream
+        m = self.model
+        word = None
+        if m.gumbel_noise_in_eval:
+            word = torch.empty(1, dtype=torch.int64, device=self.seed_state.device)
+            call("gsat_seed_next", ptr(self.seed_state), ptr(word), stream())
+        kept = m.keep_dual_att
+        m.keep_dual_att = True
+        try:
+            with torch.no_grad():
+                att, _, ld, logits = m.dual_forward_pass(pb, db, epoch, False, dual_seed=word)
+                losses = torch.stack([ld["loss"].reshape(()), ld["pred"].reshape(()), ld["info"].reshape(())]).to(torch.float32)
+                att = edge_tensor(att)
+                dual_att = m.dual_att[:att.shape[0]]
+                self.log.append(att, pb, logits, losses)
+                if self.dual_log is not None:
+                    self.dual_log.append(dual_att, pb, logits, losses)
+        finally:
+            m.keep_dual_att, m.dual_att = kept, None
+        return att, logits, losses, dual_att, word
+
+    def run_once(self, mixed: bool):
+        """The body of one captured graph, run on the current stream."""
+        from .collate import collate_padded_pair
+        clear_cache()
+        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
+        db.r = self.r
+        epoch = self.model.mix_after_epoch + (1 if mixed else 0)           # only the mix reads it: r comes from db.r
+        att, logits, losses, dual_att, word = self._forward(pb, db, epoch)
+        self._outputs[mixed] = dict(batch=pb, dual_batch=db, edge_att=att, clf_logits=logits, losses=losses, dual_att=dual_att, _word=word)
+        self._select(mixed)
+
+    def _select(self, mixed):
+        for key, v in self._outputs[mixed].items():
+            setattr(self, key, v)
+
+    def _capture(self, k, bins, max_graphs, max_edges):
+        from .collate import collate_padded_pair
+        m, ds, dev = self.model, self.primal_ds, self.primal_ds.x_all.device
+        was_sync_free = sync_free()
+        restore = _eval_mode(m)
+        set_sync_free(True)
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                pb, db = collate_padded_pair(ds, self.dual_ds, self.graph_ids, self.capacity)
+                with torch.no_grad():
+                    logit_cols = int(m.dual_forward_pass(pb, db, 0, False, dual_seed=0)[3].shape[1])
+                y_cols = int(ds.y_all.numel() // max(int(ds.y_all.shape[0]), 1))
+                mg = ds.num_graphs if max_graphs is None else int(max_graphs)
+                me = int(ds.edge_local_all.shape[1]) if max_edges is None else int(max_edges)
+                new_log = lambda: EpochLog(k, mg, me, max(-(-mg // self.batch_size), 1), logit_cols, y_cols, bins, False, dev)
+                self.log = new_log()
+                self.dual_log = new_log() if self.score_dual else None
+                for mixed in (False, True, False):          # both bodies run eagerly before either is captured
+                    self.run_once(mixed)
+            torch.cuda.current_stream().wait_stream(side)
+            if int(self.batch.valid[3]) != 0:
+                raise ValueError(f"ReplayedDualEval: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
+            self._reset_logs()
+            for mixed in (False, True):
+                with torch.cuda.graph(self.graphs[mixed]):
+                    self.run_once(mixed)
+        finally:
+            set_sync_free(was_sync_free)
+            restore()
+            clear_cache()
+            self._reset_logs()
+            self._set_seed_state(0)
+
+    def _reset_logs(self):
+        for log in (self.log, self.dual_log):
+            if log is not None:
+                log.reset()
+
+    def step(self, graph_ids, epoch: int) -> None:
+        """Evaluate the graphs ``graph_ids`` (exactly ``batch_size`` ids) at ``epoch`` -- the dual r follows its schedule, the mixed graph runs
+        when ``epoch > mix_after_epoch`` -- with the seed stream's next word, and append them to the log(s); nothing is read back.
+        ``edge_att`` [E_cap, 1], ``dual_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3], ``batch`` and ``dual_batch`` hold the
+        replay's outputs until the next replay of the same graph."""
+        ids = torch.as_tensor(graph_ids)
+        if ids.numel() != self.batch_size:
+            raise ValueError(f"ReplayedDualEval was captured for {self.batch_size} graphs per step, got {ids.numel()}")
+        self.graph_ids.copy_(ids.reshape(-1), non_blocking=True)
+        self.r.fill_(float(self._r_of(epoch)))
+        mixed = bool(epoch > self.model.mix_after_epoch)
+        self.graphs[mixed].replay()
+        self._select(mixed)
+
+    def run(self, graph_ids, epoch: int) -> dict:
+        """One evaluation epoch over ``graph_ids`` (any number, in visiting order) at ``epoch``: the seed stream restarts at (base, epoch <<
+        32) and the logs are reset; every full batch is a replay, the tail of fewer than ``batch_size`` graphs runs eagerly (both
+        datasets' ``collate``, the same eval-mode forward with the next seed word, the same appends), and ``log.compute()`` gives the
+        scores -- with ``score_dual`` also ``dual_att_auroc``, ``dual_precision@k``, ``dual_delta_kl``, ``dual_avg_signal_att_weights`` and
+        ``dual_avg_bkg_att_weights`` of the dual attention."""
+        ids = torch.as_tensor(graph_ids).reshape(-1)
+        B, n = self.batch_size, int(ids.numel())
+        self._set_seed_state(int(epoch) << 32)
+        self._reset_logs()
+        for s in range(0, n - B + 1, B):
+            self.step(ids[s:s + B], epoch)
+        if n % B:
+            restore = _eval_mode(self.model)
+            try:
+                tail = ids[n - n % B:].to(self.primal_ds.x_all.device, torch.int64)
+                self._forward(self.primal_ds.collate(tail), self.dual_ds.collate(tail), epoch)
+            finally:
+                restore()
+        res = self.log.compute()
+        if self.dual_log is not None:
+            dual = self.dual_log.compute()
+            for key in _DUAL_SCORES:
+                key = key.format(k=self.log.k)
+                res["dual_" + key] = dual[key]
+        return res

@@ -543,6 +543,18 @@ int gsat_sample_fwd(const float* logits, const float* noise, int mode, float tem
 int gsat_sample_bwd(const float* att, const float* datt, float temp, int64_t M, float* dlogits, void* stream);
 
 /*
+ * Gumbel-sigmoid (mode 2 above) whose uniform is drawn inside the kernel: U[m] = word m & 3 (x, y, z, w) of
+ * philox4x32(seed, m >> 2, 0, 5, 0x5A17) -- Philox stream 5 -- as (float)(word >> 8) * 2^-24, in [0, 1) like torch.rand; one draw
+ * serves four consecutive rows.  The seed is *seed_dev when seed_dev != NULL (a captured hipGraph draws new noise on every replay
+ * once gsat_seed_next rewrites that word), else `seed`.  att is bitwise gsat_sample_fwd(mode 2) on the U that
+ * gsat_philox_gumbel_noise reports for the same seed; the backward is gsat_sample_bwd.  16-byte loads and stores when logits and att
+ * are 16-byte aligned, scalar ones otherwise.  M == 0: no launch; M >= 2^31 or tau <= 0: GSAT_ERR_ARG.
+ */
+int gsat_gumbel_sigmoid_philox(const float* logits, int64_t M, float tau, float eps, uint64_t seed, const uint64_t* seed_dev,
+                               float* att, void* stream);
+int gsat_philox_gumbel_noise(uint64_t seed, int64_t M, float* U, void* stream);
+
+/*
  * edge_att[e] = node_att[src_e] * node_att[dst_e]
  * replaces: lift_node_att_to_edge_att (example/gsat.py:112-117, src/run_gsat.py:870-875).
  * backward walks both CSRs (no atomics): dnode[n] = sum_out d_e a[dst_e] + sum_in d_e a[src_e].
