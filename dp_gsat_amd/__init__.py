@@ -5,7 +5,7 @@ Public names follow the reference: ``get_model, GIN, PNA, GINConv, GINEConv, PNA
 ExtractorMLP, GSAT, Criterion, get_preds, reorder_like, process_data``.
 Everything computes through ``libgsat_hip.so`` (C ABI: include/gsat_hip.h); there is no CPU fallback.
 """
-from .get_model import MLP, BatchSequential, Criterion, InstanceNorm, get_model, get_preds
+from .get_model import MLP, BatchSequential, Criterion, InstanceNorm, criterion_valid, get_model, get_preds
 from .conv_layers import GINConv, GINEConv, LEConv, PNAConvSimple
 from .gin import GIN
 from .pna import PNA
@@ -33,4 +33,4 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "AttentionHistogram", "EvaluationMeter", "attention_histogram", "classifier_accuracy", "classifier_rocauc", "pr_curve",
            "task_auroc_counts", "PaddedBatch", "padded", "current_padding", "ReplayedStep",
            "ReplayedDualStep", "collate_padded_pair", "f1_sparsity_loss_valid", "EpochLog", "delta_kl_segments", "ReplayedEval",
-           "ReplayedDualEval"]
+           "ReplayedDualEval", "criterion_valid"]

@@ -95,6 +95,12 @@ SIGNATURES = {
     "gsat_f1_sparsity_bwd": (INT, [P, P, P, P, I64, P, P, P]),
     "gsat_f1_sparsity_block_entries": (I64, []),
     "gsat_f1_sparsity_max_blocks": (I64, []),
+    "gsat_criterion_fwd": (INT, [P, P, I64, I64, INT, P, P, P, P, P]),
+    "gsat_criterion_bwd": (INT, [P, P, P, P, I64, I64, INT, P, P, P]),
+    "gsat_criterion_block_items": (I64, [I64, INT]),
+    "gsat_criterion_max_blocks": (I64, []),
+    "gsat_ragged_scan": (INT, [P, I64, P, P, I64, P, P, P, P, P, P]),
+    "gsat_collate_padded_ragged": (INT, [P, I64, P, P, P, P, I64, P, P, I64, I64, P, P, P, P, P, P]),
     "gsat_collate_padded": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P, P]),
     "gsat_collate": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P]),
     "gsat_line_graph_pair_counts": (INT, [P, I64, P, P]),

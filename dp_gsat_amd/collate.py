@@ -20,7 +20,8 @@ class PaddedBatch(Batch):
     the unused node rows and edge slots, so ``num_graphs = B + 1``.  Besides the fields of ``collate``'s batch it carries ``valid``
     (int32[4] on the device: N_real, E_real, B, overflow), ``capacity = (N_cap, E_cap)``, ``node_src_row`` / ``edge_src_slot`` (the
     dataset row / slot of every node / edge, -1 for padding) and optionally ``r`` (one device float: the info loss's r) and ``pair`` (the
-    other batch of a ``collate_padded_pair``)."""
+    other batch of a ``collate_padded_pair``).  A ``ragged`` batch (``collate_padded(..., ragged=True)``) has ``B`` graph slots of which only
+    the first ``valid[2]`` are filled."""
 
 
 def _take_padded(table, index):
@@ -40,6 +41,7 @@ class PackedDataset:
         self.node_counts = self.node_ptr_all[1:] - self.node_ptr_all[:-1]
         self.edge_counts = self.edge_ptr_all[1:] - self.edge_ptr_all[:-1]
         self._capacities = {}
+        self._host_counts = None
 
     @classmethod
     def from_data_list(cls, graphs: Sequence, device) -> "PackedDataset":
@@ -86,6 +88,46 @@ class PackedDataset:
             n, e = torch.stack([self.node_counts.topk(k).values.sum(), self.edge_counts.topk(k).values.sum()]).tolist()
             self._capacities[k] = (int(n) + 2, int(e))
         return self._capacities[k]
+
+    def budget_batches(self, perm, capacity: tuple, max_graphs: int) -> torch.Tensor:
+        """The graphs ``perm`` (ids in visiting order) packed into batches of a node / edge budget, PyG's ``DynamicBatchSampler``: int64
+        [num_batches, max_graphs] on the device, one row per batch -- ``collate_padded(row, capacity, ragged=True)`` -- with -1 in the
+        unused slots.  In ``perm``'s order a graph opens a new batch when adding it would break ``nodes + 2 <= N_cap``, ``edges <=
+        E_cap`` or ``count <= max_graphs``: every batch fits, the order is kept and no batch could have taken its successor's first
+        graph.  A graph that fits no batch alone raises ValueError.
+
+        Host work: two cumulative sums over ``perm`` and three searches per batch, on a host copy of the graphs' sizes that is made the
+        first time (this dataset's only host read here)."""
+        N_cap, E_cap, slots = int(capacity[0]), int(capacity[1]), int(max_graphs)
+        if slots < 1:
+            raise ValueError("budget_batches needs at least one graph slot per batch")
+        if self._host_counts is None:
+            both = torch.stack([self.node_counts, self.edge_counts]).cpu().numpy()
+            self._host_counts = (both[0].copy(), both[1].copy())
+        import numpy as np
+        p = torch.as_tensor(perm).reshape(-1).cpu().numpy().astype(np.int64)
+        if p.size and (p.min() < 0 or p.max() >= self.num_graphs):
+            raise ValueError("budget_batches: graph ids must lie in [0, num_graphs)")
+        cn = np.concatenate([[0], np.cumsum(self._host_counts[0][p])])
+        ce = np.concatenate([[0], np.cumsum(self._host_counts[1][p])])
+        starts, s, n = [], 0, int(p.size)
+        while s < n:
+            # the first position whose running total exceeds the budget ends the batch (side="right": equality still fits)
+            end = min(int(np.searchsorted(cn, cn[s] + N_cap - 2, side="right")) - 1, int(np.searchsorted(ce, ce[s] + E_cap, side="right")) - 1,
+                      s + slots, n)
+            if end <= s:
+                g = int(p[s])
+                raise ValueError(f"budget_batches: graph {g} ({int(self._host_counts[0][g])} nodes + 2 padding nodes, "
+                                 f"{int(self._host_counts[1][g])} edges) does not fit the capacity (N_cap, E_cap) = ({N_cap}, {E_cap})")
+            starts.append(s)
+            s = end
+        starts = np.asarray(starts + [n], dtype=np.int64)
+        out = np.full((len(starts) - 1, slots), -1, dtype=np.int64)
+        if n:
+            length = np.diff(starts)
+            row = np.repeat(np.arange(len(length)), length)
+            out[row, np.arange(n) - starts[row]] = p
+        return torch.from_numpy(out).to(self.x_all.device)
 
     def pair_capacity_for(self, dual: "PackedDataset", batch_size: int) -> tuple:
         """(N_cap, E_cap, E_dual_cap) of ``collate_padded_pair`` that no batch of ``batch_size`` distinct graphs exceeds: ``capacity_for`` of
@@ -134,16 +176,23 @@ class PackedDataset:
         dual._primal = self
         return dual
 
-    def collate_padded(self, graph_ids: torch.Tensor, capacity: tuple) -> PaddedBatch:
+    def collate_padded(self, graph_ids: torch.Tensor, capacity: tuple, ragged: bool = False) -> PaddedBatch:
         """``collate(graph_ids)`` into tensors of the fixed shape ``capacity = (N_cap, E_cap)``: rows < N_real, slots < E_real and graphs
         < B are bit-identical to ``collate``; the remaining rows are zero-feature nodes of a padding graph ``B`` and the remaining slots
         a symmetric edge set among them (include/gsat_hip.h: gsat_collate_padded).  At least two padding nodes always remain.  A batch
         that does not fit raises ValueError -- in sync-free mode nothing is read back: ``valid[3]`` is set and the batch is all padding.
         No host decision is taken, so the call can be captured into a hipGraph; run the model on the result through
-        ``GSAT.forward_pass`` or inside ``dp_gsat_amd.padded(batch.valid, batch.capacity)``."""
-        return self._collate_padded(graph_ids, capacity)
+        ``GSAT.forward_pass`` or inside ``dp_gsat_amd.padded(batch.valid, batch.capacity)``.
 
-    def _collate_padded(self, graph_ids, capacity, spoil=None, check=True) -> PaddedBatch:
+        ``ragged=True``: ``graph_ids`` are ``B`` graph SLOTS and a negative id is an empty one; empty slots must be trailing.  The batch
+        still has ``num_graphs = B + 1`` (the padding graph is graph ``B``); the graphs of the empty slots have no node and no edge and a
+        zero ``y`` row, and ``valid[2]`` is the number of filled slots, counted on the device, so that one captured step takes any
+        number of graphs up to ``B`` (``GSAT.forward_pass`` hands it to the criterion).  A filled slot after an empty one makes the batch
+        an overflow like one that does not fit, and so does an id that is not below the dataset's graph count: everything is padding and
+        ``valid == (0, 0, 0, 1)``.  The batch carries ``ragged = True``."""
+        return self._collate_padded(graph_ids, capacity, ragged=bool(ragged))
+
+    def _collate_padded(self, graph_ids, capacity, spoil=None, check=True, ragged=False) -> PaddedBatch:
         """``collate_padded``; ``spoil`` (a 0-dim bool on the device) makes the batch an overflow whatever its size -- the joint verdict of a
         pair: the node total handed to the kernel is raised by the capacity, which fails its ``N + 2 <= N_cap`` test, and an overflow
         batch reads neither scan.  ``check=False`` leaves the host read of the overflow word to the caller."""
@@ -153,9 +202,22 @@ class PackedDataset:
         N_cap, E_cap = int(capacity[0]), int(capacity[1])
         if B < 1 or N_cap < 2 or E_cap < 0:
             raise ValueError("collate_padded needs at least one graph and a capacity of at least two nodes")
-        zero = torch.zeros(1, dtype=torch.int64, device=dev)
-        out_node_ptr = torch.cat([zero, self.node_counts[ids].cumsum(0)])
-        out_edge_ptr = torch.cat([zero, self.edge_counts[ids].cumsum(0)])
+        state = empty = None
+        if ragged:
+            # one launch: both scans with the empty slots counting nothing (the collation kernel gives them no row and never looks their
+            # id up), the number of filled slots, and whether a filled slot sits behind an empty one -- the verdict stays on the device
+            if spoil is not None:
+                raise ValueError("a ragged batch takes no joint overflow verdict (collate_padded_pair is not ragged)")
+            out_node_ptr, out_edge_ptr = (torch.empty(B + 1, dtype=torch.int64, device=dev) for _ in range(2))
+            state, safe = torch.empty(2, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+            empty = torch.empty(B, dtype=torch.bool, device=dev)
+            call("gsat_ragged_scan", ptr(ids), B, ptr(self.node_ptr_all), ptr(self.edge_ptr_all), self.num_graphs, ptr(out_node_ptr),
+                 ptr(out_edge_ptr), ptr(state), ptr(safe), ptr(empty), stream())
+            ids = safe
+        else:
+            zero = torch.zeros(1, dtype=torch.int64, device=dev)
+            out_node_ptr = torch.cat([zero, self.node_counts[ids].cumsum(0)])
+            out_edge_ptr = torch.cat([zero, self.edge_counts[ids].cumsum(0)])
         if spoil is not None:
             out_node_ptr[B] += spoil.to(torch.int64) * N_cap
         batch = torch.empty(N_cap, dtype=torch.int64, device=dev)
@@ -163,9 +225,13 @@ class PackedDataset:
         edge_index = torch.empty(2, E_cap, dtype=torch.int64, device=dev)
         edge_src = torch.empty(E_cap, dtype=torch.int64, device=dev)
         valid = torch.empty(4, dtype=torch.int32, device=dev)
-        call("gsat_collate_padded", ptr(ids), B, ptr(self.node_ptr_all), ptr(self.edge_ptr_all), ptr(self.edge_local_all),
-             int(self.edge_local_all.shape[1]), ptr(out_node_ptr), ptr(out_edge_ptr), N_cap, E_cap, ptr(batch), ptr(node_src),
-             ptr(edge_index) if E_cap else None, ptr(edge_src) if E_cap else None, ptr(valid), stream())
+        tail = (ptr(self.node_ptr_all), ptr(self.edge_ptr_all), ptr(self.edge_local_all), int(self.edge_local_all.shape[1]), ptr(out_node_ptr),
+                ptr(out_edge_ptr), N_cap, E_cap, ptr(batch), ptr(node_src), ptr(edge_index) if E_cap else None,
+                ptr(edge_src) if E_cap else None, ptr(valid), stream())
+        if ragged:
+            call("gsat_collate_padded_ragged", ptr(ids), B, ptr(state), *tail)
+        else:
+            call("gsat_collate_padded", ptr(ids), B, *tail)
         if check and not sync_free():
             n, e, _, overflow = valid.tolist()           # the one host read, where collate reads its sizes
             if overflow:
@@ -173,10 +239,14 @@ class PackedDataset:
                                  "(two padding nodes must remain)")
         y = None
         if self.y_all is not None:
-            y = torch.cat([self.y_all.index_select(0, ids), self.y_all.new_zeros((1,) + tuple(self.y_all.shape[1:]))])
+            rows = self.y_all.index_select(0, ids)
+            if ragged:
+                rows.masked_fill_(empty.view((-1,) + (1,) * (rows.dim() - 1)), 0)
+            y = torch.cat([rows, self.y_all.new_zeros((1,) + tuple(self.y_all.shape[1:]))])
+        extra = dict(ragged=True) if ragged else {}
         return PaddedBatch(x=_take_padded(self.x_all, node_src), edge_index=edge_index, batch=batch, y=y,
                            edge_attr=_take_padded(self.edge_attr_all, edge_src), edge_label=_take_padded(self.edge_label_all, edge_src),
-                           num_graphs=B + 1, valid=valid, capacity=(N_cap, E_cap), node_src_row=node_src, edge_src_slot=edge_src)
+                           num_graphs=B + 1, valid=valid, capacity=(N_cap, E_cap), node_src_row=node_src, edge_src_slot=edge_src, **extra)
 
 
 def collate_padded_pair(primal: PackedDataset, dual: PackedDataset, graph_ids: torch.Tensor, capacity: Optional[tuple] = None):

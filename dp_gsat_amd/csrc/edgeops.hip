@@ -340,16 +340,22 @@ __global__ void k_collate_edges(const int64_t* __restrict__ ids, const int64_t* 
 // Fixed-capacity batch: the real part as k_collate_*, then padding nodes (graph id G, source row -1) and a symmetric padding edge set
 // among them (source slot -1).  Thread i takes node row i and edge slot i; thread 0 writes valid = (N_real, E_real, G, overflow).
 // A batch that does not fit (fewer than two padding nodes left, or more edges than slots) becomes all padding with overflow = 1.
+// Graphs without rows are skipped by seg_of and their ids never read, which is what lets trailing slots stay empty (k_ragged_scan).
 __global__ void k_collate_padded(const int64_t* __restrict__ ids, const int64_t* __restrict__ node_ptr_all,
                                  const int64_t* __restrict__ edge_ptr_all, const int64_t* __restrict__ edge_local_all, int64_t E_all,
                                  const int64_t* __restrict__ out_node_ptr, const int64_t* __restrict__ out_edge_ptr, int G, int64_t N_cap,
                                  int64_t E_cap, int64_t* __restrict__ batch, int64_t* __restrict__ node_src_row,
-                                 int64_t* __restrict__ edge_index, int64_t* __restrict__ edge_src_slot, int32_t* __restrict__ valid) {
+                                 int64_t* __restrict__ edge_index, int64_t* __restrict__ edge_src_slot, int32_t* __restrict__ valid,
+                                 const int64_t* __restrict__ ragged) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t N = out_node_ptr[G], E = out_edge_ptr[G];
-    const bool overflow = N + 2 > N_cap || E > E_cap;
+    const bool overflow = N + 2 > N_cap || E > E_cap || (ragged && ragged[1] != 0);
     if (overflow) N = E = 0;
-    if (i == 0) { valid[0] = (int32_t)N; valid[1] = (int32_t)E; valid[2] = G; valid[3] = overflow ? 1 : 0; }
+    if (i == 0) {
+        // a ragged batch (ragged != NULL: filled slots, spoiled) counts its filled slots, none when it overflowed
+        const int32_t graphs = ragged ? (overflow ? 0 : (int32_t)min<int64_t>(max<int64_t>(ragged[0], 0), G)) : G;
+        valid[0] = (int32_t)N; valid[1] = (int32_t)E; valid[2] = graphs; valid[3] = overflow ? 1 : 0;
+    }
     if (i < N_cap) {
         if (i < N) {
             const int g = seg_of(out_node_ptr, G, i);
@@ -382,24 +388,113 @@ __global__ void k_collate_padded(const int64_t* __restrict__ ids, const int64_t*
     }
 }
 
+// The scans of a ragged batch in ONE block: slot i of ids holds a graph id or, negative, nothing.  out_node_ptr / out_edge_ptr [B + 1]
+// are the exclusive scans of the slots' node / edge counts with empty slots counting 0, safe_ids the ids with 0 in the empty slots,
+// empty[i] = 1 for an empty slot, state = (filled slots, spoiled): spoiled when a filled slot follows an empty one or an id is not
+// below G_all (such a slot counts nothing and is never looked up).  Chunks of RSB slots, a Hillis-Steele scan in LDS per chunk and a
+// running carry: integer sums, so the order does not matter.
+constexpr int RSB = 256;
+
+__global__ __launch_bounds__(RSB) void k_ragged_scan(const int64_t* __restrict__ ids, int B, const int64_t* __restrict__ node_ptr_all,
+                                                     const int64_t* __restrict__ edge_ptr_all, int64_t G_all,
+                                                     int64_t* __restrict__ out_node_ptr, int64_t* __restrict__ out_edge_ptr,
+                                                     int64_t* __restrict__ state, int64_t* __restrict__ safe_ids,
+                                                     uint8_t* __restrict__ empty) {
+    __shared__ int64_t sn[RSB], se[RSB];
+    __shared__ int s_filled, s_first_empty, s_last_filled, s_bad;
+    const int t = threadIdx.x;
+    if (t == 0) { s_filled = 0; s_first_empty = 0x7fffffff; s_last_filled = -1; s_bad = 0; }
+    int64_t carry_n = 0, carry_e = 0;
+    int filled = 0, first_empty = 0x7fffffff, last_filled = -1, bad = 0;
+    for (int base = 0; base < B; base += RSB) {
+        const int i = base + t;
+        int64_t n = 0, e = 0;
+        if (i < B) {
+            const int64_t id = ids[i];
+            const bool ok = id >= 0 && id < G_all;
+            if (ok) {
+                n = node_ptr_all[id + 1] - node_ptr_all[id];
+                e = edge_ptr_all[id + 1] - edge_ptr_all[id];
+            }
+            if (id >= 0) { ++filled; last_filled = i; } else { first_empty = min(first_empty, i); }
+            if (id >= G_all) bad = 1;
+            safe_ids[i] = ok ? id : 0;
+            empty[i] = id < 0 ? 1 : 0;
+        }
+        __syncthreads();                                    // the previous chunk's totals have been read
+        sn[t] = n; se[t] = e;
+        __syncthreads();
+        for (int o = 1; o < RSB; o <<= 1) {
+            const int64_t a = t >= o ? sn[t - o] : 0, b = t >= o ? se[t - o] : 0;
+            __syncthreads();
+            sn[t] += a; se[t] += b;
+            __syncthreads();
+        }
+        if (i < B) { out_node_ptr[i + 1] = carry_n + sn[t]; out_edge_ptr[i + 1] = carry_e + se[t]; }
+        carry_n += sn[RSB - 1]; carry_e += se[RSB - 1];
+    }
+    __syncthreads();
+    atomicAdd(&s_filled, filled);                           // integer LDS atomics: any order gives the same result
+    atomicMin(&s_first_empty, first_empty);
+    atomicMax(&s_last_filled, last_filled);
+    atomicOr(&s_bad, bad);
+    __syncthreads();
+    if (t == 0) {
+        out_node_ptr[0] = 0; out_edge_ptr[0] = 0;
+        state[0] = s_filled;
+        state[1] = (s_bad || s_last_filled > s_first_empty) ? 1 : 0;
+    }
+}
+
 }  // namespace gsat
 
 extern "C" {
+
+int gsat_ragged_scan(const int64_t* graph_ids, int64_t num_slots, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
+                     int64_t num_graphs_all, int64_t* out_node_ptr, int64_t* out_edge_ptr, int64_t* state, int64_t* safe_ids,
+                     uint8_t* empty, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(num_slots >= 1 && num_slots < (1ll << 31) - 1 && num_graphs_all >= 0, GSAT_ERR_ARG, "gsat_ragged_scan: bad extents");
+    GSAT_REQUIRE(graph_ids && node_ptr_all && edge_ptr_all && out_node_ptr && out_edge_ptr && state && safe_ids && empty, GSAT_ERR_ARG,
+                 "gsat_ragged_scan: null pointer");
+    gsat::k_ragged_scan<<<1, gsat::RSB, 0, stream>>>(graph_ids, (int)num_slots, node_ptr_all, edge_ptr_all, num_graphs_all, out_node_ptr,
+                                                     out_edge_ptr, state, safe_ids, empty);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+static int collate_padded_impl(const char* name, const int64_t* graph_ids, int64_t num_graphs, const int64_t* ragged_state,
+                               const int64_t* node_ptr_all, const int64_t* edge_ptr_all, const int64_t* edge_local_all, int64_t num_edges_all,
+                               const int64_t* out_node_ptr, const int64_t* out_edge_ptr, int64_t N_cap, int64_t E_cap, int64_t* batch,
+                               int64_t* node_src_row, int64_t* edge_index, int64_t* edge_src_slot, int32_t* valid, hipStream_t stream) {
+    GSAT_REQUIRE(num_graphs >= 1 && num_graphs < (1ll << 31) - 1 && N_cap >= 2 && N_cap < (1ll << 31) && E_cap >= 0 && E_cap < (1ll << 31),
+                 GSAT_ERR_ARG, "%s: bad extents (at least one graph, two padding nodes)", name);
+    GSAT_REQUIRE(graph_ids && node_ptr_all && edge_ptr_all && out_node_ptr && out_edge_ptr && batch && node_src_row && valid &&
+                 (E_cap == 0 || (edge_local_all && edge_index && edge_src_slot)), GSAT_ERR_ARG, "%s: null pointer", name);
+    gsat::k_collate_padded<<<GRID1(std::max(N_cap, E_cap))>>>(graph_ids, node_ptr_all, edge_ptr_all, edge_local_all, num_edges_all, out_node_ptr,
+                                                              out_edge_ptr, (int)num_graphs, N_cap, E_cap, batch, node_src_row, edge_index,
+                                                              edge_src_slot, valid, ragged_state);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
 
 int gsat_collate_padded(const int64_t* graph_ids, int64_t num_graphs, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
                         const int64_t* edge_local_all, int64_t num_edges_all, const int64_t* out_node_ptr, const int64_t* out_edge_ptr,
                         int64_t N_cap, int64_t E_cap, int64_t* batch, int64_t* node_src_row, int64_t* edge_index, int64_t* edge_src_slot,
                         int32_t* valid, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GSAT_REQUIRE(num_graphs >= 1 && num_graphs < (1ll << 31) - 1 && N_cap >= 2 && N_cap < (1ll << 31) && E_cap >= 0 && E_cap < (1ll << 31),
-                 GSAT_ERR_ARG, "gsat_collate_padded: bad extents (at least one graph, two padding nodes)");
-    GSAT_REQUIRE(graph_ids && node_ptr_all && edge_ptr_all && out_node_ptr && out_edge_ptr && batch && node_src_row && valid &&
-                 (E_cap == 0 || (edge_local_all && edge_index && edge_src_slot)), GSAT_ERR_ARG, "gsat_collate_padded: null pointer");
-    gsat::k_collate_padded<<<GRID1(std::max(N_cap, E_cap))>>>(graph_ids, node_ptr_all, edge_ptr_all, edge_local_all, num_edges_all, out_node_ptr,
-                                                              out_edge_ptr, (int)num_graphs, N_cap, E_cap, batch, node_src_row, edge_index,
-                                                              edge_src_slot, valid);
-    GSAT_LAUNCH_CHECK();
-    return GSAT_OK;
+    return collate_padded_impl("gsat_collate_padded", graph_ids, num_graphs, nullptr, node_ptr_all, edge_ptr_all, edge_local_all, num_edges_all,
+                               out_node_ptr, out_edge_ptr, N_cap, E_cap, batch, node_src_row, edge_index, edge_src_slot, valid,
+                               (hipStream_t)stream_);
+}
+
+int gsat_collate_padded_ragged(const int64_t* graph_ids, int64_t num_graphs, const int64_t* ragged_state, const int64_t* node_ptr_all,
+                               const int64_t* edge_ptr_all, const int64_t* edge_local_all, int64_t num_edges_all,
+                               const int64_t* out_node_ptr, const int64_t* out_edge_ptr, int64_t N_cap, int64_t E_cap, int64_t* batch,
+                               int64_t* node_src_row, int64_t* edge_index, int64_t* edge_src_slot, int32_t* valid, void* stream_) {
+    GSAT_REQUIRE(ragged_state, GSAT_ERR_ARG, "gsat_collate_padded_ragged: null pointer");
+    return collate_padded_impl("gsat_collate_padded_ragged", graph_ids, num_graphs, ragged_state, node_ptr_all, edge_ptr_all, edge_local_all,
+                               num_edges_all, out_node_ptr, out_edge_ptr, N_cap, E_cap, batch, node_src_row, edge_index, edge_src_slot, valid,
+                               (hipStream_t)stream_);
 }
 
 int gsat_collate(const int64_t* graph_ids, int64_t num_graphs, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 from . import _lib
 from ._lib import call, ptr, stream
 from .graph_index import call_size
-from .ops import InstanceNormFn
+from .ops import CriterionLoss, InstanceNormFn
 
 
 class _SegmentCache:
@@ -100,13 +100,36 @@ class Criterion(nn.Module):
         self.num_class = num_class
         self.multi_label = multi_label
 
-    def forward(self, logits, targets):
+    def forward(self, logits, targets, g_valid=None):
+        """``g_valid`` (one int32 on the device): the criterion of the first ``g_valid`` rows alone, through libgsat_hip
+        (``criterion_valid``) -- the graph count of a ragged batch; None: the reference's torch arithmetic."""
+        if g_valid is not None:
+            return criterion_valid(logits, targets, self.num_class, self.multi_label, g_valid)
         if self.num_class == 2 and not self.multi_label:
             return F.binary_cross_entropy_with_logits(logits, targets.float())
         if self.num_class > 2 and not self.multi_label:
             return F.cross_entropy(logits, targets.long())
         is_labeled = targets == targets          # NaN marks unlabeled entries
         return F.binary_cross_entropy_with_logits(logits[is_labeled], targets[is_labeled].float())
+
+
+def criterion_valid(logits, targets, num_class, multi_label=False, g_valid=None):
+    """``Criterion(num_class, multi_label)(logits, targets)`` over the rows ``< g_valid`` (one int32 on the device, clamped to the row
+    count; None: every row) as two HIP launches and one for the backward.  Nothing is read back and no row at or beyond the count is
+    loaded, so a captured step can take a different number of graphs on every replay.  The mean's divisor is clamped to 1: no row (or,
+    multi-label, no labelled entry) gives the loss 0 and zero gradients where torch gives NaN.  A cross-entropy label outside
+    [0, num_class) gives a NaN loss."""
+    if logits.dim() == 1:
+        logits = logits.view(-1, 1)
+    if multi_label:
+        mode = 2
+    elif num_class == 2:
+        mode = 0
+    elif num_class > 2:
+        mode = 1
+    else:
+        raise ValueError("criterion_valid: num_class must be at least 2")
+    return CriterionLoss.apply(logits, targets, mode, g_valid)
 
 
 def get_preds(logits, multi_label):

@@ -158,8 +158,8 @@ class GSAT(nn.Module):
         self.decay_r = decay_r
         self.sync_loss_dict = True       # the reference calls .item() three times per step (example/gsat.py:34)
 
-    def __loss__(self, att, clf_logits, clf_labels, epoch, loss_weights=None, r_dev=None):
-        pred_loss = self.criterion(clf_logits, clf_labels)
+    def __loss__(self, att, clf_logits, clf_labels, epoch, loss_weights=None, r_dev=None, g_valid=None):
+        pred_loss = self.criterion(clf_logits, clf_labels) if g_valid is None else self.criterion(clf_logits, clf_labels, g_valid=g_valid)
         r = self.get_r(self.decay_interval, self.decay_r, epoch, final_r=self.final_r)
         if current_padding() is None:
             i_loss = info_loss(att, r)
@@ -183,7 +183,9 @@ class GSAT(nn.Module):
 
         A padded batch (one with a ``valid`` field, PackedDataset.collate_padded) runs inside ``padded(data.valid)``: BatchNorm and the info
         loss count its real rows, the criterion sees the real graphs ``[:B]``, and ``data.r`` -- one float on the device, when present -- is
-        the info loss's r instead of get_r(epoch).  Every returned tensor has capacity shape; callers slice with the counts."""
+        the info loss's r instead of get_r(epoch).  Every returned tensor has capacity shape; callers slice with the counts.  On a
+        ``ragged`` batch (``collate_padded(..., ragged=True)``) the criterion takes the ``B`` graph slots and reads how many are filled from
+        ``valid[2]`` on the device (``criterion_valid``)."""
         valid = getattr(data, "valid", None)
         if valid is not None:
             if getattr(self.criterion, "multi_label", False):
@@ -209,8 +211,9 @@ class GSAT(nn.Module):
         if real_graphs is None:
             loss, loss_dict = self.__loss__(att, clf_logits, data.y, epoch, loss_weights)
         else:           # static slices: the padding graph is the last one and B is a host int
+            g_valid = data.valid[2:3] if getattr(data, "ragged", False) else None        # filled slots, read by the criterion kernel
             loss, loss_dict = self.__loss__(att, clf_logits[:real_graphs], data.y[:real_graphs], epoch, loss_weights,
-                                            r_dev=getattr(data, "r", None))
+                                            r_dev=getattr(data, "r", None), g_valid=g_valid)
         return edge_att, loss, loss_dict, clf_logits
 
     @staticmethod

@@ -697,6 +697,40 @@ class F1SparsityLoss(torch.autograd.Function):
         return da, None, None
 
 
+class CriterionLoss(torch.autograd.Function):
+    """The classification criterion (src/utils/get_model.py:19-34) over the first ``g_valid`` rows of ``logits`` [G, C] (one int32 on the
+    device; None: all rows).  ``mode`` 0: binary cross entropy with logits, 1: cross entropy (``target`` [G] holds the class), 2: BCE over
+    the entries whose target is not NaN.  Two launches forward, one backward, bitwise repeatable; rows beyond the count are not read and
+    get a zero gradient; an empty selection gives the loss 0; the target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target, mode, g_valid=None):
+        z, y = _f32c(logits), _f32c(target.detach())
+        if z.dim() != 2 or z.numel() == 0:
+            raise ValueError("criterion: logits must be a non-empty [G, C] tensor")
+        G, C = int(z.shape[0]), int(z.shape[1])
+        if y.numel() != (G if mode == 1 else G * C):
+            raise ValueError("criterion: the target needs one entry per row (cross entropy) or per logit")
+        if g_valid is not None and (g_valid.dtype != torch.int32 or g_valid.numel() != 1 or not g_valid.is_cuda):
+            raise ValueError("g_valid must be one int32 on the device")
+        out = torch.empty((), dtype=torch.float32, device=z.device)
+        stats = torch.empty(4, dtype=torch.float32, device=z.device)
+        partial = torch.empty(512, dtype=torch.float32, device=z.device)
+        call("gsat_criterion_fwd", ptr(z), ptr(y), G, C, int(mode), ptr(g_valid), ptr(partial), ptr(out), ptr(stats), stream())
+        ctx.save_for_backward(z, y, stats)
+        ctx.mode, ctx.g_valid = int(mode), g_valid
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        z, y, stats = ctx.saved_tensors
+        gout = _f32c(gout)
+        dz = torch.empty_like(z)
+        call("gsat_criterion_bwd", ptr(z), ptr(y), ptr(stats), ptr(gout), int(z.shape[0]), int(z.shape[1]), ctx.mode, ptr(ctx.g_valid),
+             ptr(dz), stream())
+        return dz, None, None, None
+
+
 class InstanceNormFn(torch.autograd.Function):
     """per-graph InstanceNorm (eps 1e-5, no affine, batch statistics always) -- src/utils/get_model.py:50-51."""
 

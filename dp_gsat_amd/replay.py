@@ -48,6 +48,28 @@ def _padded_pair_setup(m, primal_ds, dual_ds, batch_size, capacity):
     return batch_size, cap
 
 
+def _first_budget_row(dataset, capacity, batch_size):
+    """The ids a ragged instance warms up and captures on: the first batch budget batching cuts from the dataset in storage order."""
+    return dataset.budget_batches(torch.arange(dataset.num_graphs), capacity, batch_size)[0].contiguous()
+
+
+def _load_ids(self, graph_ids, who):
+    """Copy ``graph_ids`` into the static id buffer of a replayed step.  Ragged: 1 .. batch_size ids (or a row of ``budget_batches`` with
+    its -1s), the remaining slots are emptied with -1; else exactly batch_size ids."""
+    ids = torch.as_tensor(graph_ids).reshape(-1)
+    n = int(ids.numel())
+    if self.ragged:
+        if not 1 <= n <= self.batch_size:
+            raise ValueError(f"{who} was captured for 1 to {self.batch_size} graphs per step, got {n}")
+        if n < self.batch_size:
+            self.graph_ids[n:].fill_(-1)
+        self.graph_ids[:n].copy_(ids, non_blocking=True)
+        return
+    if n != self.batch_size:
+        raise ValueError(f"{who} was captured for {self.batch_size} graphs per step, got {n}")
+    self.graph_ids.copy_(ids, non_blocking=True)
+
+
 class ReplayedStep:
     """``ReplayedStep(gsat, dataset, batch_size, capacity=None)``: captures clear_cache, collate_padded, forward_pass,
     zero_grad(set_to_none=True), backward and optimizer.step() of ``gsat`` on ``dataset`` (a PackedDataset) once, after three warm-up
@@ -65,9 +87,18 @@ class ReplayedStep:
 
     After a step: ``loss`` (device scalar), ``clf_logits`` [B + 1, C], ``batch`` (the PaddedBatch, ``batch.valid`` holds the counts) and,
     with ``keep_edge_att=True``, ``edge_att`` [E_cap, 1] -- all of capacity shape and overwritten by the next replay.
-    ``graph``: an own ``torch.cuda.CUDAGraph`` to capture into (one with debug mode on, to dump it)."""
+    ``graph``: an own ``torch.cuda.CUDAGraph`` to capture into (one with debug mode on, to dump it).
 
-    def __init__(self, gsat, dataset, batch_size: int, capacity: Optional[tuple] = None, keep_edge_att: bool = False, graph=None):
+    ``ragged=True``: ``batch_size`` is a number of graph SLOTS.  The graph holds ``collate_padded(..., ragged=True)`` and the criterion
+    reads the number of filled slots on the device, so ``step`` takes 1 to ``batch_size`` ids and no tail batch is left to run eagerly.
+    ``batches(perm)`` packs an epoch into batches that fit the capacity (``PackedDataset.budget_batches``), which is what lets the
+    capacity be sized near the mean batch instead of the worst one.  Warm-up and capture run on the first such batch of the dataset in
+    storage order, so a capacity that graphs 0 .. batch_size-1 exceed is fine.  An overflow batch has no filled slot: its loss is exactly
+    0 and neither loss term produces a gradient (the optimizer still steps on the weight decay, and BatchNorm still sees an empty
+    batch)."""
+
+    def __init__(self, gsat, dataset, batch_size: int, capacity: Optional[tuple] = None, keep_edge_att: bool = False, graph=None,
+                 ragged: bool = False):
         opt = gsat.optimizer
         if opt is None or not all(g.get("capturable", False) for g in opt.param_groups):
             raise ValueError("ReplayedStep needs a capturable optimizer, e.g. torch.optim.Adam(params, capturable=True, fused=True)")
@@ -78,7 +109,11 @@ class ReplayedStep:
             raise ValueError("batch_size must be between 1 and the dataset's graph count")
         self.capacity = tuple(int(c) for c in capacity) if capacity is not None else dataset.capacity_for(self.batch_size)
         dev = dataset.x_all.device
-        self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
+        self.ragged = bool(ragged)
+        if self.ragged:
+            self.graph_ids = _first_budget_row(dataset, self.capacity, self.batch_size)
+        else:
+            self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
         self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
         self.keep_edge_att = bool(keep_edge_att)
         self.batch = self.loss = self.clf_logits = self.edge_att = None
@@ -94,7 +129,7 @@ class ReplayedStep:
         """The step body (what the graph holds), run on the current stream."""
         gsat = self.gsat
         clear_cache()
-        b = self.dataset.collate_padded(self.graph_ids, self.capacity)
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
         b.r = self.r
         self._overflow.bitwise_or_(b.valid[3:4])
         att, loss, _, logits = gsat.forward_pass(b, 0, True)
@@ -141,15 +176,16 @@ class ReplayedStep:
                 self._overflow.zero_()
 
     def step(self, graph_ids, epoch: int) -> torch.Tensor:
-        """One training step on the graphs ``graph_ids`` (exactly ``batch_size`` ids; tensor, array or list) with r = get_r(epoch).
-        Returns the device loss; nothing is read back."""
-        ids = torch.as_tensor(graph_ids)
-        if ids.numel() != self.batch_size:
-            raise ValueError(f"ReplayedStep was captured for {self.batch_size} graphs per step, got {ids.numel()}")
-        self.graph_ids.copy_(ids.reshape(-1), non_blocking=True)
+        """One training step on the graphs ``graph_ids`` (exactly ``batch_size`` ids -- ragged: 1 to ``batch_size``, or a row of ``batches``;
+        tensor, array or list) with r = get_r(epoch).  Returns the device loss; nothing is read back."""
+        _load_ids(self, graph_ids, "ReplayedStep")
         self.r.fill_(float(self._r_of(epoch)))
         self.graph.replay()
         return self.loss
+
+    def batches(self, perm) -> torch.Tensor:
+        """``dataset.budget_batches(perm, self.capacity, self.batch_size)``: the rows to feed ``step`` of a ragged instance."""
+        return self.dataset.budget_batches(perm, self.capacity, self.batch_size)
 
     def overflowed(self) -> bool:
         """True if a step since the last call (or since capture) got a batch that did not fit the capacity.  One host read; clears
@@ -187,10 +223,13 @@ class ReplayedEval:
     append that does not fit the log, is refused on the device and raised by ``run`` / ``log.compute()``.
 
     Refused with ValueError, like the padded path: the multi-label criterion, ``sync_group`` BatchNorm, and ``DualGSAT`` (see
-    ``ReplayedDualEval``)."""
+    ``ReplayedDualEval``).
+
+    ``ragged=True``: as in ``ReplayedStep`` -- ``batch_size`` graph slots, ``step`` takes 1 to ``batch_size`` ids, and ``run`` packs its ids
+    with ``budget_batches`` and replays EVERY batch: there is no eager tail.  The log then has room for one batch per graph."""
 
     def __init__(self, gsat, dataset, batch_size: int, k: int, capacity: Optional[tuple] = None, bins: int = 64,
-                 max_graphs: Optional[int] = None, max_edges: Optional[int] = None, graph=None):
+                 max_graphs: Optional[int] = None, max_edges: Optional[int] = None, graph=None, ragged: bool = False):
         if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
             raise ValueError("ReplayedEval replays GSAT.forward_pass; the dual/primal evaluation (DualGSAT) is ReplayedDualEval's")
         if getattr(gsat.criterion, "multi_label", False):
@@ -204,7 +243,11 @@ class ReplayedEval:
             raise ValueError("batch_size must be between 1 and the dataset's graph count")
         self.capacity = tuple(int(c) for c in capacity) if capacity is not None else dataset.capacity_for(self.batch_size)
         dev = dataset.x_all.device
-        self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
+        self.ragged = bool(ragged)
+        if self.ragged:
+            self.graph_ids = _first_budget_row(dataset, self.capacity, self.batch_size)
+        else:
+            self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
         self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
         self.batch = self.clf_logits = self.edge_att = self.losses = None
         self.graph = graph if graph is not None else torch.cuda.CUDAGraph()
@@ -224,7 +267,7 @@ class ReplayedEval:
     def run_once(self):
         """The body of the captured graph, run on the current stream."""
         clear_cache()
-        b = self.dataset.collate_padded(self.graph_ids, self.capacity)
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
         b.r = self.r
         self.edge_att, self.clf_logits, self.losses = self._forward(b, 0)
         self.batch = b
@@ -242,13 +285,15 @@ class ReplayedEval:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                b = ds.collate_padded(self.graph_ids, self.capacity)
+                b = ds.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
                 with torch.no_grad():
                     logit_cols = int(gsat.forward_pass(b, 0, False)[3].shape[1])
                 y_cols = int(ds.y_all.numel() // max(int(ds.y_all.shape[0]), 1))
                 mg = ds.num_graphs if max_graphs is None else int(max_graphs)
                 me = int(ds.edge_local_all.shape[1]) if max_edges is None else int(max_edges)
-                self.log = EpochLog(k, mg, me, max(-(-mg // self.batch_size), 1), logit_cols, y_cols, bins, False, dev)
+                # budget batching may close a batch after any graph: at worst one graph per batch
+                most = mg if self.ragged else -(-mg // self.batch_size)
+                self.log = EpochLog(k, mg, me, max(most, 1), logit_cols, y_cols, bins, False, dev)
                 for _ in range(3):
                     self.run_once()
             torch.cuda.current_stream().wait_stream(side)
@@ -265,22 +310,27 @@ class ReplayedEval:
                 self.log.reset()
 
     def step(self, graph_ids, epoch: int) -> None:
-        """Evaluate the graphs ``graph_ids`` (exactly ``batch_size`` ids) with r = get_r(epoch) and append them to ``log``; nothing is read
+        """Evaluate the graphs ``graph_ids`` (exactly ``batch_size`` ids; ragged: 1 to ``batch_size``) with r = get_r(epoch) and append them to ``log``; nothing is read
         back.  ``edge_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3] and ``batch`` hold the replay's outputs until the next."""
-        ids = torch.as_tensor(graph_ids)
-        if ids.numel() != self.batch_size:
-            raise ValueError(f"ReplayedEval was captured for {self.batch_size} graphs per step, got {ids.numel()}")
-        self.graph_ids.copy_(ids.reshape(-1), non_blocking=True)
+        _load_ids(self, graph_ids, "ReplayedEval")
         self.r.fill_(float(self._r_of(epoch)))
         self.graph.replay()
+
+    def batches(self, perm) -> torch.Tensor:
+        """``dataset.budget_batches(perm, self.capacity, self.batch_size)``: the rows to feed ``step`` of a ragged instance."""
+        return self.dataset.budget_batches(perm, self.capacity, self.batch_size)
 
     def run(self, graph_ids, epoch: int) -> dict:
         """One evaluation epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, the
         tail of fewer than ``batch_size`` graphs runs eagerly (``dataset.collate``, the same eval-mode forward, the same append), and
-        ``log.compute()`` -- two host reads -- gives the scores."""
+        ``log.compute()`` -- two host reads -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
         ids = torch.as_tensor(graph_ids).reshape(-1)
         B, n = self.batch_size, int(ids.numel())
         self.log.reset()
+        if self.ragged:
+            for row in self.batches(ids):
+                self.step(row, epoch)
+            return self.log.compute()
         for s in range(0, n - B + 1, B):
             self.step(ids[s:s + B], epoch)
         if n % B:

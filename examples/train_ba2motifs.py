@@ -15,8 +15,13 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
   * dp_gsat_amd.ReplayedEval (``--graph``) -- the periodic test evaluation replays a second captured graph (collation, eval-mode forward,
     append to a device log) batch by batch and scores the log once: two host reads per evaluation.
 
+  * ``--graph --ragged`` -- no eager batch at all: both captured graphs take a ragged graph count (``ragged=True``), an epoch is cut
+    into batches that fill a node / edge budget (PackedDataset.budget_batches, at most ``--batch-size`` graphs each) and the capacity
+    is sized from the data (the mean graph times the batch size) instead of from the worst batch.
+
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged
 """
 import argparse
 import os
@@ -68,11 +73,14 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, one GPU per rank) or gloo (to rehearse N ranks on one GPU)")
     ap.add_argument("--graph", action="store_true", help="train full batches as replays of one captured hipGraph (single process)")
+    ap.add_argument("--ragged", action="store_true", help="with --graph: budget batches of a ragged graph count, every batch a replay")
     args = ap.parse_args()
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if args.graph and world > 1:
         ap.error("--graph is single-process: it replays one captured step and cannot shard a batch over ranks")
+    if args.ragged and not args.graph:
+        ap.error("--ragged batches are replays: it needs --graph")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     if world > 1:
@@ -113,20 +121,33 @@ def main():
         return acc, auc, prec
 
     replayed = replayed_eval = None
-    if args.graph and n_train >= args.batch_size:
+    if args.ragged:
+        # the budget of a batch: batch_size graphs of the mean size (never less than the largest graph alone); one host read
+        slots = min(args.batch_size, len(graphs))
+        n_mean, e_mean, n_max, e_max = torch.stack([ds.node_counts.double().mean(), ds.edge_counts.double().mean(),
+                                                    ds.node_counts.max().double(), ds.edge_counts.max().double()]).tolist()
+        capacity = (max(int(np.ceil(n_mean * slots)), int(n_max)) + 2, max(int(np.ceil(e_mean * slots)), int(e_max)))
+        replayed = G.ReplayedStep(gsat, ds, slots, capacity=capacity, ragged=True)
+        replayed_eval = G.ReplayedEval(gsat, ds, slots, 5, capacity=capacity, ragged=True)
+    elif args.graph and n_train >= args.batch_size:
         replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
-    if args.graph:
+    if args.graph and not args.ragged:
         replayed_eval = G.ReplayedEval(gsat, ds, min(args.batch_size, len(graphs)), 5)
 
     def evaluate_replayed(ids, epoch):
-        res = replayed_eval.run(ids, epoch)                       # full batches: replays; the tail: eager; one scoring pass at the end
+        res = replayed_eval.run(ids, epoch)      # full batches: replays; the tail: eager (--ragged: a replay too); one scoring pass at the end
         return res["clf_acc"], res["att_auroc"], res["precision@5"]
 
     gen = np.random.RandomState(args.seed)                        # identical permutations on every rank
     for epoch in range(args.epochs):
         perm = gen.permutation(n_train)
         tot, nb = 0.0, 0
-        for s in range(0, n_train, args.batch_size):
+        if args.ragged:
+            for row in replayed.batches(perm):                    # every batch fits the capacity and is a replay; the tail included
+                tot, nb = tot + replayed.step(row, epoch), nb + 1
+            if replayed.overflowed():
+                raise RuntimeError("a budget batch overflowed its capacity")
+        for s in ([] if args.ragged else range(0, n_train, args.batch_size)):
             ids = perm[s:s + args.batch_size]
             if replayed is not None and len(ids) == args.batch_size:
                 tot, nb = tot + replayed.step(ids, epoch), nb + 1   # the loss stays on the device: no host read per step

@@ -609,6 +609,29 @@ int gsat_f1_sparsity_bwd(const float* p, const float* y, const float* stats, con
 int64_t gsat_f1_sparsity_block_entries(void);
 int64_t gsat_f1_sparsity_max_blocks(void);
 
+/*
+ * The classification criterion (src/utils/get_model.py:19-34) over the first b rows of logits [G, C]: b = *g_valid_dev (int32 on the
+ * device, clamped to [0, G]) or G when g_valid_dev is NULL; rows at or beyond b are not read.
+ *   mode 0 (binary):      mean over the b C entries of max(z, 0) - z y + log1p(exp(-|z|)); target float[G, C].
+ *   mode 1 (cross entropy): mean over the b rows of logsumexp(z_row) - z_row[y] (max-subtracted); target float[G] holds the class index.
+ *                         An index outside [0, C) (or NaN) makes the loss NaN and is never used as an offset.
+ *   mode 2 (multi-label): mode 0's term over the entries whose target is not NaN, divided by their number in the rows < b.
+ * The divisor is clamped to at least 1: an empty selection gives the loss 0 and zero gradients (torch gives NaN), as in
+ * gsat_info_loss_valid_*.  partial: scratch float[512] (sums, then the counts as uint32 bits).  stats float[4] = (sum, divisor,
+ * 1 / divisor, 0) feeds the backward: dlogits = gout[0] (sigmoid(z) - y) / divisor (modes 0, 2; 0 on unlabelled entries) or
+ * gout[0] (softmax(z_row) - onehot(y)) / divisor (mode 1; NaN over a row whose label is no class), and exactly 0 in every row >= b
+ * whatever it holds (the target is a label: no gradient).  Two-stage sums in a fixed order, no atomics: equal inputs give equal bits.
+ * Kernels only (no memset / memcpy), nothing is read back: capturable.  One first-stage block covers gsat_criterion_block_items(C, mode)
+ * entries (modes 0, 2) or rows (mode 1; 4 lanes per row for C <= 16, else 64) until gsat_criterion_max_blocks() blocks are in use.
+ * 1 <= G <= 2^20 and 1 <= C <= 1024 (GSAT_ERR_UNSUPPORTED beyond, never a truncation).
+ */
+int gsat_criterion_fwd(const float* logits, const float* target, int64_t G, int64_t C, int mode, const int32_t* g_valid_dev,
+                       float* partial, float* loss, float* stats, void* stream);
+int gsat_criterion_bwd(const float* logits, const float* target, const float* stats, const float* gout, int64_t G, int64_t C, int mode,
+                       const int32_t* g_valid_dev, float* dlogits, void* stream);
+int64_t gsat_criterion_block_items(int64_t C, int mode);
+int64_t gsat_criterion_max_blocks(void);
+
 /* out[i] = (int32) in[i] */
 int gsat_narrow_i64(const int64_t* in, int64_t n, int32_t* out, void* stream);
 
@@ -641,6 +664,28 @@ int gsat_collate_padded(const int64_t* graph_ids, int64_t num_graphs, const int6
                         const int64_t* edge_local_all, int64_t num_edges_all, const int64_t* out_node_ptr,
                         const int64_t* out_edge_ptr, int64_t N_cap, int64_t E_cap, int64_t* batch, int64_t* node_src_row,
                         int64_t* edge_index, int64_t* edge_src_slot, int32_t* valid, void* stream);
+
+/*
+ * The two scans of a ragged batch in one launch (one block).  graph_ids int64[num_slots]: a graph id, or a negative value for an EMPTY
+ * slot.  out_node_ptr / out_edge_ptr int64[num_slots + 1] = exclusive scans of the slots' node / edge counts, an empty slot counting 0;
+ * safe_ids int64[num_slots] = the ids with 0 in the empty slots; empty uint8[num_slots] = 1 for an empty slot; state int64[2] =
+ * (number of filled slots, spoiled).  spoiled = 1 when a filled slot follows an empty one (empty slots must be trailing) or an id is
+ * not below num_graphs_all; such an id counts nothing and is never used as an offset.  Integer sums: bitwise repeatable; capturable.
+ */
+int gsat_ragged_scan(const int64_t* graph_ids, int64_t num_slots, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
+                     int64_t num_graphs_all, int64_t* out_node_ptr, int64_t* out_edge_ptr, int64_t* state, int64_t* safe_ids,
+                     uint8_t* empty, void* stream);
+
+/*
+ * gsat_collate_padded with a graph count read on the device: ragged_state int64[2] = (filled slots, spoiled) and the scans are
+ * gsat_ragged_scan's, so the empty slots own no node and no edge and their graph_ids entries are never dereferenced.  valid[2] = the
+ * number of filled slots; a spoiled batch is an overflow like one that does not fit, and an overflow batch has valid == (0, 0, 0, 1).
+ * Padding nodes still get graph id num_graphs.
+ */
+int gsat_collate_padded_ragged(const int64_t* graph_ids, int64_t num_graphs, const int64_t* ragged_state, const int64_t* node_ptr_all,
+                               const int64_t* edge_ptr_all, const int64_t* edge_local_all, int64_t num_edges_all,
+                               const int64_t* out_node_ptr, const int64_t* out_edge_ptr, int64_t N_cap, int64_t E_cap, int64_t* batch,
+                               int64_t* node_src_row, int64_t* edge_index, int64_t* edge_src_slot, int32_t* valid, void* stream);
 
 /*
  * Line ("dual") graph: dual node k = primal directed edge k; dual edges join, in both directions, every two primal
