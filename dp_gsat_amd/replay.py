@@ -3,49 +3,109 @@
 A captured step bakes N, E and G into every launch, and real batches differ in N and E from step to step.  ``ReplayedStep`` collates
 every batch to a fixed capacity (PackedDataset.collate_padded) inside the captured graph, so that a step is: copy the graph ids, set
 r, replay.  The padding is arithmetically inert.
+
+The four public classes say what their graphs hold (``run_once``) and what they refuse; the protocol around it -- static inputs, warm-up
+on a side stream, capture, putting everything back, ``step`` -- is ``_Replayed`` and the module's functions, each written once.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Optional
 
 import torch
 
+from ._lib import call, ptr, stream
+from .collate import collate_padded_pair
 from .eval_log import EpochLog
 from .graph_index import clear_cache, set_sync_free, sync_free
 from .gsat import get_r
 from .ops import edge_tensor
 
+_MULTI_LABEL = "a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)"
 
-def _eval_mode(model):
-    """Switch every module of ``model`` to eval mode and its sync_loss_dict off; returns what puts both back."""
-    modes = [(m, m.training) for m in model.modules()]
+
+# ---- what capturing changes, and what puts it back -------------------------------------------------------------------------------------------
+@contextmanager
+def _kept_training_state(model, optimizers):
+    """Whatever trains inside the block is undone on exit, normal or by exception: parameters, buffers and every tensor of the
+    optimizers' state are copied back in place (a captured graph holds their addresses), and state tensors that did not exist on entry
+    are zeroed."""
+    tensors = list(model.parameters()) + list(model.buffers())
+    saved = [t.detach().clone() for t in tensors]
+    had_state = {id(p): {k: v.clone() for k, v in opt.state[p].items() if isinstance(v, torch.Tensor)}
+                 for opt in optimizers for grp in opt.param_groups for p in grp["params"] if p in opt.state}
+    try:
+        yield
+    finally:
+        with torch.no_grad():
+            for t, s in zip(tensors, saved):
+                t.copy_(s)
+            for opt in optimizers:
+                for grp in opt.param_groups:
+                    for p in grp["params"]:
+                        for k, v in opt.state.get(p, {}).items():
+                            if isinstance(v, torch.Tensor):
+                                old = had_state.get(id(p), {}).get(k)
+                                v.copy_(old) if old is not None else v.zero_()
+
+
+@contextmanager
+def _forward_mode(model, evaluating):
+    """``sync_loss_dict`` off (the loss dict stays on the device) and, ``evaluating``, every module in ``eval()``; both are put back on
+    exit.  What an evaluator's eager tail runs under."""
+    modes = [(m, m.training) for m in model.modules()] if evaluating else []
     was_loss_dict = model.sync_loss_dict
-    model.eval()
+    if evaluating:
+        model.eval()
     model.sync_loss_dict = False
-
-    def restore():
+    try:
+        yield
+    finally:
         for m, t in modes:
             m.training = t
         model.sync_loss_dict = was_loss_dict
-    return restore
 
 
-def _padded_pair_setup(m, primal_ds, dual_ds, batch_size, capacity):
-    """The refusals of a replayed padded pair (those ``DualGSAT._pair_forward_pass`` makes, before anything is captured); returns
-    (batch_size, capacity) as an int and a triple of ints."""
+@contextmanager
+def _capture_mode(model, evaluating=False):
+    """What warm-up and capture run under: ``sync_free`` on and ``_forward_mode``.  On exit all of it is put back and the index cache is
+    emptied."""
+    was_sync_free = sync_free()
+    set_sync_free(True)
+    try:
+        with _forward_mode(model, evaluating):
+            yield
+    finally:
+        set_sync_free(was_sync_free)
+        clear_cache()
+
+
+# ---- refusals, and what the two pair classes share ------------------------------------------------------------------------------------------
+def _need_capturable(opt, what):
+    if opt is None or not all(g.get("capturable", False) for g in opt.param_groups):
+        raise ValueError(f"{what}, e.g. torch.optim.Adam(params, capturable=True, fused=True)")
+
+
+def _refuse_sync_group(model):
+    if any(getattr(m, "sync_group", None) for m in model.modules()):
+        raise ValueError("a padded batch cannot take sync_group BatchNorm (its statistics are reduced over ranks on the host's schedule)")
+
+
+def _mix_epoch(m, mixed):
+    """The epoch a captured pair body passes on.  Only the mix reads it: r comes from db.r."""
+    return m.mix_after_epoch + (1 if mixed else 0)
+
+
+def _padded_pair_setup(obj, m, primal_ds, dual_ds, batch_size, capacity, graphs):
+    """The refusals of a replayed padded pair (those ``DualGSAT._pair_forward_pass`` makes, before anything is captured), then the
+    static inputs of the pair on ``obj``."""
     if m.primal_criterion.multi_label or m.dual_criterion.multi_label:
-        raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
+        raise ValueError(_MULTI_LABEL)
     if m.primal_learn_edge_att or m.dual_learn_edge_att:
         raise ValueError("a padded pair takes node attention on both sides (the MUTAG configs), not edge attention")
     primal_ds.check_pair(dual_ds)
-    batch_size = int(batch_size)
-    if not 1 <= batch_size <= primal_ds.num_graphs:
-        raise ValueError("batch_size must be between 1 and the dataset's graph count")
-    cap = capacity if capacity is not None else primal_ds.pair_capacity_for(dual_ds, batch_size)
-    cap = tuple(int(c) for c in cap)
-    if len(cap) != 3:
-        raise ValueError("capacity is (N_cap, E_cap, E_dual_cap)")
-    return batch_size, cap
+    obj.model, obj.primal_ds, obj.dual_ds = m, primal_ds, dual_ds
+    obj._setup(m, (primal_ds, dual_ds), batch_size, capacity, graphs)
 
 
 def _first_budget_row(dataset, capacity, batch_size):
@@ -53,24 +113,150 @@ def _first_budget_row(dataset, capacity, batch_size):
     return dataset.budget_batches(torch.arange(dataset.num_graphs), capacity, batch_size)[0].contiguous()
 
 
-def _load_ids(self, graph_ids, who):
-    """Copy ``graph_ids`` into the static id buffer of a replayed step.  Ragged: 1 .. batch_size ids (or a row of ``budget_batches`` with
-    its -1s), the remaining slots are emptied with -1; else exactly batch_size ids."""
-    ids = torch.as_tensor(graph_ids).reshape(-1)
-    n = int(ids.numel())
-    if self.ragged:
-        if not 1 <= n <= self.batch_size:
-            raise ValueError(f"{who} was captured for 1 to {self.batch_size} graphs per step, got {n}")
-        if n < self.batch_size:
-            self.graph_ids[n:].fill_(-1)
-        self.graph_ids[:n].copy_(ids, non_blocking=True)
-        return
-    if n != self.batch_size:
-        raise ValueError(f"{who} was captured for {self.batch_size} graphs per step, got {n}")
-    self.graph_ids.copy_(ids, non_blocking=True)
+class _Replayed:
+    """What the four classes share: the static inputs of the captured graphs (``graph_ids``, ``r``), the warm-up-and-capture driver and
+    ``step``.  A class with one graph is the pair (unmixed, mixed) without its mixed half.  A subclass gives ``run_once`` -- the body a
+    graph holds, which ends in ``_publish`` -- and says in its constructor what it refuses."""
+
+    def _setup(self, model, datasets, batch_size, capacity, graphs, ragged=False):
+        """Validate ``batch_size`` and ``capacity`` and make the static inputs.  ``datasets``: (dataset,) for one graph (``graphs`` is
+        that graph or None), (primal, dual) for the unmixed/mixed pair (``graphs`` is the pair or None)."""
+        ds = datasets[0]
+        self._model, self._datasets, self._pair = model, datasets, len(datasets) == 2
+        self.batch_size = int(batch_size)
+        if not 1 <= self.batch_size <= ds.num_graphs:
+            raise ValueError("batch_size must be between 1 and the dataset's graph count")
+        if capacity is None:
+            capacity = ds.pair_capacity_for(datasets[1], self.batch_size) if self._pair else ds.capacity_for(self.batch_size)
+        self.capacity = tuple(int(c) for c in capacity)
+        if self._pair and len(self.capacity) != 3:
+            raise ValueError("capacity is (N_cap, E_cap, E_dual_cap)")
+        dev = ds.x_all.device
+        self.ragged = bool(ragged)
+        if self.ragged:
+            self.graph_ids = _first_budget_row(ds, self.capacity, self.batch_size)
+        else:
+            self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
+        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
+        if self._pair:
+            unmixed, mixed = graphs if graphs is not None else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
+            self.graphs = self._graphs = {False: unmixed, True: mixed}
+        else:
+            self.graph = graphs if graphs is not None else torch.cuda.CUDAGraph()
+            self._graphs = {False: self.graph}
+        self._outputs, self._current = {}, None
+
+    def _r_of(self, epoch):
+        m = self._model
+        if not self._pair:
+            return get_r(m.decay_interval, m.decay_r, epoch, final_r=m.final_r)
+        return m.dual_fix_r if m.dual_fix_r else get_r(m.dual_decay_interval, m.dual_decay_r, epoch, final_r=m.dual_final_r,
+                                                       init_r=m.dual_init_r)
+
+    def _body(self, mixed):
+        if self._pair:
+            self.run_once(mixed)
+        else:
+            self.run_once()
+
+    def _publish(self, mixed, **outputs):
+        """The end of ``run_once``: ``outputs`` are what the graph ``mixed`` leaves behind, and become attributes."""
+        self._outputs[mixed] = outputs
+        self._select(mixed)
+
+    def _select(self, mixed):
+        for key, v in self._outputs[mixed].items():
+            setattr(self, key, v)
+        self._current = mixed
+
+    def _warm_up_and_capture(self, setup=None, before_capture=None):
+        """Three eager runs on a side stream -- of the one body, or unmixed, mixed, unmixed: both bodies run eagerly before either is
+        captured -- after ``setup()`` on that stream; the one host read that tells whether the warm-up batch fit; ``before_capture()``;
+        then one capture per graph, with no reseeding in between: both graphs draw from the one device seed stream."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            if setup is not None:
+                setup()
+            for mixed in ((False, True, False) if self._pair else (False, False, False)):
+                self._body(mixed)
+        torch.cuda.current_stream().wait_stream(side)
+        if int(self.batch.valid[3]) != 0:
+            raise ValueError(f"{type(self).__name__}: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
+        if before_capture is not None:
+            before_capture()
+        for mixed, graph in self._graphs.items():
+            with torch.cuda.graph(graph):
+                self._body(mixed)
+
+    def _load_ids(self, graph_ids):
+        """Copy ``graph_ids`` into the static id buffer.  Ragged: 1 .. batch_size ids (or a row of ``budget_batches`` with its -1s), the
+        remaining slots are emptied with -1; else exactly batch_size ids."""
+        ids = torch.as_tensor(graph_ids).reshape(-1)
+        n = int(ids.numel())
+        if self.ragged:
+            if not 1 <= n <= self.batch_size:
+                raise ValueError(f"{type(self).__name__} was captured for 1 to {self.batch_size} graphs per step, got {n}")
+            if n < self.batch_size:
+                self.graph_ids[n:].fill_(-1)
+            self.graph_ids[:n].copy_(ids, non_blocking=True)
+            return
+        if n != self.batch_size:
+            raise ValueError(f"{type(self).__name__} was captured for {self.batch_size} graphs per step, got {n}")
+        self.graph_ids.copy_(ids, non_blocking=True)
+
+    def step(self, graph_ids, epoch: int) -> Optional[torch.Tensor]:
+        """One replay on the graphs ``graph_ids`` (exactly ``batch_size`` ids -- ragged: 1 to ``batch_size``, or a row of ``batches``;
+        tensor, array or list) with r = get_r(epoch); of a pair, the dual r follows its schedule and the mixed graph runs when ``epoch >
+        mix_after_epoch``.  Nothing is read back.  A training class returns the device loss; an evaluator appends to its log(s) -- a dual
+        one with the seed stream's next word -- and returns None.  The attributes the class docstring lists hold the replay's outputs
+        until the next replay of the same graph."""
+        self._load_ids(graph_ids)
+        self.r.fill_(float(self._r_of(epoch)))
+        mixed = self._pair and bool(epoch > self._model.mix_after_epoch)
+        self._graphs[mixed].replay()
+        if self._current is not mixed:          # the other graph of the pair ran last: its outputs are published
+            self._select(mixed)
+        return self._outputs[mixed].get("loss")
+
+    def batches(self, perm) -> torch.Tensor:
+        """``dataset.budget_batches(perm, self.capacity, self.batch_size)``: the rows to feed ``step`` of a ragged instance."""
+        return self._datasets[0].budget_batches(perm, self.capacity, self.batch_size)
+
+    def check_epoch(self, perm) -> None:
+        """Raise ValueError if a full batch of the epoch ``perm`` (graph ids in visiting order) exceeds the capacity -- in nodes, edges
+        or, of a pair, dual edges: the totals of every ``perm[k * batch_size : (k + 1) * batch_size]`` are taken on the device and read
+        back once."""
+        ds, B = self._datasets[0], self.batch_size
+        p = torch.as_tensor(perm).to(ds.x_all.device, torch.int64).reshape(-1)
+        full = int(p.numel()) // B
+        if full == 0:
+            return
+        p = p[: full * B].view(full, B)
+        counts = [ds.node_counts, ds.edge_counts] + [d.edge_counts for d in self._datasets[1:]]
+        n, *e = torch.stack([c[p].sum(1).max() for c in counts]).tolist()
+        if n + 2 > self.capacity[0] or any(v > c for v, c in zip(e, self.capacity[1:])):
+            names = ", ".join(("N", "E", "E_dual")[:len(counts)])
+            raise ValueError(f"a batch of this epoch needs ({names}) = ({n} + 2 padding nodes, {', '.join(map(str, e))}), above the "
+                             f"capacity {self.capacity}")
 
 
-class ReplayedStep:
+# ---- the training classes ---------------------------------------------------------------------------------------------------------------------
+def _capture_training(rs, optimizers):
+    """Make the overflow flag of a training class and capture its graphs; nothing has trained afterwards."""
+    rs._overflow = torch.zeros(1, dtype=torch.int32, device=rs.r.device)
+    with _kept_training_state(rs._model, optimizers), _capture_mode(rs._model):
+        rs._warm_up_and_capture()
+    rs._overflow.zero_()
+
+
+def _take_overflow(rs):
+    seen = bool(int(rs._overflow))
+    rs._overflow.zero_()
+    return seen
+
+
+class ReplayedStep(_Replayed):
     """``ReplayedStep(gsat, dataset, batch_size, capacity=None)``: captures clear_cache, collate_padded, forward_pass,
     zero_grad(set_to_none=True), backward and optimizer.step() of ``gsat`` on ``dataset`` (a PackedDataset) once, after three warm-up
     runs on a side stream.  ``gsat.optimizer`` must be capturable (``torch.optim.Adam(..., capturable=True)``).  The warm-up runs
@@ -99,31 +285,14 @@ class ReplayedStep:
 
     def __init__(self, gsat, dataset, batch_size: int, capacity: Optional[tuple] = None, keep_edge_att: bool = False, graph=None,
                  ragged: bool = False):
-        opt = gsat.optimizer
-        if opt is None or not all(g.get("capturable", False) for g in opt.param_groups):
-            raise ValueError("ReplayedStep needs a capturable optimizer, e.g. torch.optim.Adam(params, capturable=True, fused=True)")
+        _need_capturable(gsat.optimizer, "ReplayedStep needs a capturable optimizer")
         if getattr(gsat.criterion, "multi_label", False):
-            raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
-        self.gsat, self.dataset, self.batch_size = gsat, dataset, int(batch_size)
-        if not 1 <= self.batch_size <= dataset.num_graphs:
-            raise ValueError("batch_size must be between 1 and the dataset's graph count")
-        self.capacity = tuple(int(c) for c in capacity) if capacity is not None else dataset.capacity_for(self.batch_size)
-        dev = dataset.x_all.device
-        self.ragged = bool(ragged)
-        if self.ragged:
-            self.graph_ids = _first_budget_row(dataset, self.capacity, self.batch_size)
-        else:
-            self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
-        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
+            raise ValueError(_MULTI_LABEL)
+        self.gsat, self.dataset = gsat, dataset
+        self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
         self.keep_edge_att = bool(keep_edge_att)
         self.batch = self.loss = self.clf_logits = self.edge_att = None
-        self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.graph = graph if graph is not None else torch.cuda.CUDAGraph()
-        self._capture()
-
-    def _r_of(self, epoch):
-        g = self.gsat
-        return get_r(g.decay_interval, g.decay_r, epoch, final_r=g.final_r)
+        _capture_training(self, (gsat.optimizer,))
 
     def run_once(self):
         """The step body (what the graph holds), run on the current stream."""
@@ -136,214 +305,16 @@ class ReplayedStep:
         gsat.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         gsat.optimizer.step()
-        self.batch, self.loss, self.clf_logits = b, loss.detach(), logits.detach()
-        if self.keep_edge_att:
-            self.edge_att = edge_tensor(att).detach()
-
-    def _capture(self):
-        gsat, opt = self.gsat, self.gsat.optimizer
-        tensors = [t for t in list(gsat.parameters()) + list(gsat.buffers())]
-        saved = [t.detach().clone() for t in tensors]
-        had_state = {id(p): {k: v.clone() for k, v in opt.state[p].items() if isinstance(v, torch.Tensor)}
-                     for grp in opt.param_groups for p in grp["params"] if p in opt.state}
-        was_sync_free, was_loss_dict = sync_free(), gsat.sync_loss_dict
-        set_sync_free(True)
-        gsat.sync_loss_dict = False
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    self.run_once()
-            torch.cuda.current_stream().wait_stream(side)
-            if int(self.batch.valid[3]) != 0:
-                raise ValueError(f"ReplayedStep: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
-            with torch.cuda.graph(self.graph):
-                self.run_once()
-        finally:
-            set_sync_free(was_sync_free)
-            gsat.sync_loss_dict = was_loss_dict
-            clear_cache()
-            with torch.no_grad():          # also when capturing failed; in place: the graph holds these addresses
-                for t, s in zip(tensors, saved):
-                    t.copy_(s)
-                for grp in opt.param_groups:
-                    for p in grp["params"]:
-                        for k, v in opt.state.get(p, {}).items():
-                            if isinstance(v, torch.Tensor):
-                                old = had_state.get(id(p), {}).get(k)
-                                v.copy_(old) if old is not None else v.zero_()
-                self._overflow.zero_()
-
-    def step(self, graph_ids, epoch: int) -> torch.Tensor:
-        """One training step on the graphs ``graph_ids`` (exactly ``batch_size`` ids -- ragged: 1 to ``batch_size``, or a row of ``batches``;
-        tensor, array or list) with r = get_r(epoch).  Returns the device loss; nothing is read back."""
-        _load_ids(self, graph_ids, "ReplayedStep")
-        self.r.fill_(float(self._r_of(epoch)))
-        self.graph.replay()
-        return self.loss
-
-    def batches(self, perm) -> torch.Tensor:
-        """``dataset.budget_batches(perm, self.capacity, self.batch_size)``: the rows to feed ``step`` of a ragged instance."""
-        return self.dataset.budget_batches(perm, self.capacity, self.batch_size)
+        self._publish(False, batch=b, loss=loss.detach(), clf_logits=logits.detach(),
+                      edge_att=edge_tensor(att).detach() if self.keep_edge_att else None)
 
     def overflowed(self) -> bool:
         """True if a step since the last call (or since capture) got a batch that did not fit the capacity.  One host read; clears
         the flag."""
-        seen = bool(int(self._overflow))
-        self._overflow.zero_()
-        return seen
-
-    def check_epoch(self, perm) -> None:
-        """Raise ValueError if a full batch of the epoch ``perm`` (graph ids in visiting order) exceeds the capacity: the (N, E) totals of
-        every ``perm[k * batch_size : (k + 1) * batch_size]`` are taken on the device and read back once."""
-        ds, B = self.dataset, self.batch_size
-        p = torch.as_tensor(perm).to(ds.x_all.device, torch.int64).reshape(-1)
-        full = int(p.numel()) // B
-        if full == 0:
-            return
-        p = p[: full * B].view(full, B)
-        n, e = torch.stack([ds.node_counts[p].sum(1).max(), ds.edge_counts[p].sum(1).max()]).tolist()
-        if n + 2 > self.capacity[0] or e > self.capacity[1]:
-            raise ValueError(f"a batch of this epoch needs (N, E) = ({n} + 2 padding nodes, {e}), above the capacity {self.capacity}")
+        return _take_overflow(self)
 
 
-class ReplayedEval:
-    """``ReplayedEval(gsat, dataset, batch_size, k, capacity=None, bins=64, max_graphs=None, max_edges=None)``: an evaluation epoch over
-    ``dataset`` (a PackedDataset with ``edge_label_all``) as replays of ONE captured hipGraph that holds clear_cache, collate_padded,
-    ``gsat.forward_pass(b, 0, False)`` under ``torch.no_grad()`` with every module in ``eval()`` mode, and ``log.append`` into an
-    :class:`~dp_gsat_amd.eval_log.EpochLog` (``log``).  Three warm-up runs on a side stream precede the capture; the modules' training
-    flags, ``sync_free`` and ``sync_loss_dict`` are put back afterwards and the log is reset.  No optimizer is needed.
-
-    The graph reads the parameters and the BatchNorm running statistics where they live, so a replay after ``ReplayedStep.step`` (or an
-    eager optimizer step) scores the new weights.  It writes none of them, draws no noise and no dropout mask, and leaves the device seed
-    stream alone: evaluating between training steps does not change the training run.
-
-    ``max_graphs`` / ``max_edges`` (the log's capacities) default to the dataset's totals; a batch that does not fit ``capacity``, or an
-    append that does not fit the log, is refused on the device and raised by ``run`` / ``log.compute()``.
-
-    Refused with ValueError, like the padded path: the multi-label criterion, ``sync_group`` BatchNorm, and ``DualGSAT`` (see
-    ``ReplayedDualEval``).
-
-    ``ragged=True``: as in ``ReplayedStep`` -- ``batch_size`` graph slots, ``step`` takes 1 to ``batch_size`` ids, and ``run`` packs its ids
-    with ``budget_batches`` and replays EVERY batch: there is no eager tail.  The log then has room for one batch per graph."""
-
-    def __init__(self, gsat, dataset, batch_size: int, k: int, capacity: Optional[tuple] = None, bins: int = 64,
-                 max_graphs: Optional[int] = None, max_edges: Optional[int] = None, graph=None, ragged: bool = False):
-        if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
-            raise ValueError("ReplayedEval replays GSAT.forward_pass; the dual/primal evaluation (DualGSAT) is ReplayedDualEval's")
-        if getattr(gsat.criterion, "multi_label", False):
-            raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
-        if any(getattr(m, "sync_group", None) for m in gsat.modules()):
-            raise ValueError("a padded batch cannot take sync_group BatchNorm (its statistics are reduced over ranks on the host's schedule)")
-        if dataset.edge_label_all is None or dataset.y_all is None:
-            raise ValueError("ReplayedEval needs a dataset with edge labels and graph labels")
-        self.gsat, self.dataset, self.batch_size = gsat, dataset, int(batch_size)
-        if not 1 <= self.batch_size <= dataset.num_graphs:
-            raise ValueError("batch_size must be between 1 and the dataset's graph count")
-        self.capacity = tuple(int(c) for c in capacity) if capacity is not None else dataset.capacity_for(self.batch_size)
-        dev = dataset.x_all.device
-        self.ragged = bool(ragged)
-        if self.ragged:
-            self.graph_ids = _first_budget_row(dataset, self.capacity, self.batch_size)
-        else:
-            self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
-        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
-        self.batch = self.clf_logits = self.edge_att = self.losses = None
-        self.graph = graph if graph is not None else torch.cuda.CUDAGraph()
-        self._capture(int(k), int(bins), max_graphs, max_edges)
-
-    _r_of = ReplayedStep._r_of
-
-    def _forward(self, b, epoch):
-        """Append the eval-mode forward of batch ``b`` to the log; the modules are in eval mode and sync_loss_dict is off."""
-        with torch.no_grad():
-            att, _, ld, logits = self.gsat.forward_pass(b, epoch, False)
-            losses = torch.stack([ld["loss"].reshape(()), ld["pred"].reshape(()), ld["info"].reshape(())]).to(torch.float32)
-            att = edge_tensor(att)
-            self.log.append(att, b, logits, losses)
-        return att, logits, losses
-
-    def run_once(self):
-        """The body of the captured graph, run on the current stream."""
-        clear_cache()
-        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
-        b.r = self.r
-        self.edge_att, self.clf_logits, self.losses = self._forward(b, 0)
-        self.batch = b
-
-    def _eval_mode(self):
-        """Switch every module to eval mode and sync_loss_dict off; returns what puts both back."""
-        return _eval_mode(self.gsat)
-
-    def _capture(self, k, bins, max_graphs, max_edges):
-        gsat, ds, dev = self.gsat, self.dataset, self.dataset.x_all.device
-        was_sync_free = sync_free()
-        restore = self._eval_mode()
-        set_sync_free(True)
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                b = ds.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
-                with torch.no_grad():
-                    logit_cols = int(gsat.forward_pass(b, 0, False)[3].shape[1])
-                y_cols = int(ds.y_all.numel() // max(int(ds.y_all.shape[0]), 1))
-                mg = ds.num_graphs if max_graphs is None else int(max_graphs)
-                me = int(ds.edge_local_all.shape[1]) if max_edges is None else int(max_edges)
-                # budget batching may close a batch after any graph: at worst one graph per batch
-                most = mg if self.ragged else -(-mg // self.batch_size)
-                self.log = EpochLog(k, mg, me, max(most, 1), logit_cols, y_cols, bins, False, dev)
-                for _ in range(3):
-                    self.run_once()
-            torch.cuda.current_stream().wait_stream(side)
-            if int(self.batch.valid[3]) != 0:
-                raise ValueError(f"ReplayedEval: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
-            self.log.reset()
-            with torch.cuda.graph(self.graph):
-                self.run_once()
-        finally:
-            set_sync_free(was_sync_free)
-            restore()
-            clear_cache()
-            if getattr(self, "log", None) is not None:
-                self.log.reset()
-
-    def step(self, graph_ids, epoch: int) -> None:
-        """Evaluate the graphs ``graph_ids`` (exactly ``batch_size`` ids; ragged: 1 to ``batch_size``) with r = get_r(epoch) and append them to ``log``; nothing is read
-        back.  ``edge_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3] and ``batch`` hold the replay's outputs until the next."""
-        _load_ids(self, graph_ids, "ReplayedEval")
-        self.r.fill_(float(self._r_of(epoch)))
-        self.graph.replay()
-
-    def batches(self, perm) -> torch.Tensor:
-        """``dataset.budget_batches(perm, self.capacity, self.batch_size)``: the rows to feed ``step`` of a ragged instance."""
-        return self.dataset.budget_batches(perm, self.capacity, self.batch_size)
-
-    def run(self, graph_ids, epoch: int) -> dict:
-        """One evaluation epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, the
-        tail of fewer than ``batch_size`` graphs runs eagerly (``dataset.collate``, the same eval-mode forward, the same append), and
-        ``log.compute()`` -- two host reads -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
-        ids = torch.as_tensor(graph_ids).reshape(-1)
-        B, n = self.batch_size, int(ids.numel())
-        self.log.reset()
-        if self.ragged:
-            for row in self.batches(ids):
-                self.step(row, epoch)
-            return self.log.compute()
-        for s in range(0, n - B + 1, B):
-            self.step(ids[s:s + B], epoch)
-        if n % B:
-            restore = self._eval_mode()
-            try:
-                tail = ids[n - n % B:].to(self.dataset.x_all.device, torch.int64)
-                self._forward(self.dataset.collate(tail), epoch)
-            finally:
-                restore()
-        return self.log.compute()
-
-
-class ReplayedDualStep:
+class ReplayedDualStep(_Replayed):
     """``ReplayedDualStep(dual_gsat, primal_ds, dual_ds, batch_size, capacity=None)``: the dual/primal training step (DualGSAT) over a
     dataset and its dual (``primal_ds.line_graph_dataset()``) as replays of captured hipGraphs.  One replay holds clear_cache,
     collate_padded_pair, dual_forward_pass, both zero_grad(set_to_none=True), the backward and both optimizer steps.  Both optimizers
@@ -368,13 +339,9 @@ class ReplayedDualStep:
                  keep_edge_att: bool = False, graphs=None):
         m = dual_gsat
         for side, opt in (("primal", m.primal_optimizer), ("dual", m.dual_optimizer)):
-            if opt is None or not all(g.get("capturable", False) for g in opt.param_groups):
-                raise ValueError(f"ReplayedDualStep needs a capturable {side} optimizer, e.g. torch.optim.Adam(params, capturable=True, fused=True)")
-        self.batch_size, self.capacity = _padded_pair_setup(m, primal_ds, dual_ds, batch_size, capacity)
-        self.model, self.primal_ds, self.dual_ds = m, primal_ds, dual_ds
+            _need_capturable(opt, f"ReplayedDualStep needs a capturable {side} optimizer")
+        _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs)
         dev = primal_ds.x_all.device
-        self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
-        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
         self.keep_edge_att, self.pinned = bool(keep_edge_att), bool(pinned)
         self.primal_noise = self.dual_noise = self.primal_masks = self.dual_masks = None
         if self.pinned:
@@ -384,11 +351,8 @@ class ReplayedDualStep:
             self.primal_masks = self._keep_masks(m.primal_extractor, N_cap, dev)
             self.dual_masks = self._keep_masks(m.dual_extractor, E_cap + 2, dev)
         self.batch = self.dual_batch = self.loss = self.clf_logits = self.edge_att = None
-        self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
-        unmixed, mixed = graphs if graphs is not None else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
-        self.graphs = {False: unmixed, True: mixed}
-        self._outputs, self._grads, self._current = {}, {}, None
-        self._capture()
+        self._grads = {}
+        _capture_training(self, (m.primal_optimizer, m.dual_optimizer))
 
     @staticmethod
     def _keep_masks(extractor, rows, dev):
@@ -396,116 +360,149 @@ class ReplayedDualStep:
         keep = 1.0 - float(extractor.mlp.dropout_p)
         return [(torch.rand(rows, int(l.weight.shape[0]), device=dev) < keep).float() for l in (l1, l2)]
 
-    def _r_of(self, epoch):
-        m = self.model
-        return m.dual_fix_r if m.dual_fix_r else get_r(m.dual_decay_interval, m.dual_decay_r, epoch, final_r=m.dual_final_r,
-                                                       init_r=m.dual_init_r)
-
-    def _params(self):
-        return [p for grp in self.model.primal_optimizer.param_groups + self.model.dual_optimizer.param_groups for p in grp["params"]]
-
     def run_once(self, mixed: bool):
         """The step body (what one graph holds), run on the current stream."""
-        from .collate import collate_padded_pair
         m = self.model
         clear_cache()
         pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
         db.r = self.r
         self._overflow.bitwise_or_(pb.valid[3:4])
-        epoch = m.mix_after_epoch + (1 if mixed else 0)           # only the mix reads it: r comes from db.r
-        att, loss, _, logits = m.dual_forward_pass(pb, db, epoch, True, self.primal_noise, self.dual_noise, self.primal_masks,
-                                                   self.dual_masks)
+        att, loss, _, logits = m.dual_forward_pass(pb, db, _mix_epoch(m, mixed), True, self.primal_noise, self.dual_noise,
+                                                   self.primal_masks, self.dual_masks)
         m.primal_optimizer.zero_grad(set_to_none=True)
         m.dual_optimizer.zero_grad(set_to_none=True)
         loss.backward()
         m.primal_optimizer.step()
         m.dual_optimizer.step()
-        out = dict(batch=pb, dual_batch=db, loss=loss.detach(), clf_logits=logits.detach(),
-                   edge_att=edge_tensor(att).detach() if self.keep_edge_att else None)
-        self._outputs[mixed] = out
-        self._grads[mixed] = [p.grad for p in self._params()]
-        self._select(mixed)
+        self._grads[mixed] = [(p, p.grad) for opt in (m.primal_optimizer, m.dual_optimizer) for grp in opt.param_groups
+                              for p in grp["params"]]
+        self._publish(mixed, batch=pb, dual_batch=db, loss=loss.detach(), clf_logits=logits.detach(),
+                      edge_att=edge_tensor(att).detach() if self.keep_edge_att else None)
 
     def _select(self, mixed):
-        for k, v in self._outputs[mixed].items():
-            setattr(self, k, v)
-        if self._current is not mixed:
-            for p, g in zip(self._params(), self._grads[mixed]):
-                p.grad = g
-            self._current = mixed
-
-    def _capture(self):
-        m = self.model
-        opts = (m.primal_optimizer, m.dual_optimizer)
-        tensors = list(m.parameters()) + list(m.buffers())
-        saved = [t.detach().clone() for t in tensors]
-        had_state = {id(p): {k: v.clone() for k, v in opt.state[p].items() if isinstance(v, torch.Tensor)}
-                     for opt in opts for grp in opt.param_groups for p in grp["params"] if p in opt.state}
-        was_sync_free, was_loss_dict = sync_free(), m.sync_loss_dict
-        set_sync_free(True)
-        m.sync_loss_dict = False
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for mixed in (False, True, False):          # both bodies run eagerly before either is captured
-                    self.run_once(mixed)
-            torch.cuda.current_stream().wait_stream(side)
-            if int(self.batch.valid[3]) != 0:
-                raise ValueError(f"ReplayedDualStep: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
-            for mixed in (False, True):                     # no reseeding in between: both graphs draw from the one device seed stream
-                self._current = None
-                with torch.cuda.graph(self.graphs[mixed]):
-                    self.run_once(mixed)
-        finally:
-            set_sync_free(was_sync_free)
-            m.sync_loss_dict = was_loss_dict
-            clear_cache()
-            with torch.no_grad():          # also when capturing failed; in place: the graphs hold these addresses
-                for t, s in zip(tensors, saved):
-                    t.copy_(s)
-                for opt in opts:
-                    for grp in opt.param_groups:
-                        for p in grp["params"]:
-                            for k, v in opt.state.get(p, {}).items():
-                                if isinstance(v, torch.Tensor):
-                                    old = had_state.get(id(p), {}).get(k)
-                                    v.copy_(old) if old is not None else v.zero_()
-                self._overflow.zero_()
-
-    def step(self, graph_ids, epoch: int) -> torch.Tensor:
-        """One training step on the graphs ``graph_ids`` (exactly ``batch_size`` ids) at ``epoch``: the dual r follows its schedule and the
-        mixed graph runs when ``epoch > mix_after_epoch``.  Returns the device loss; nothing is read back."""
-        ids = torch.as_tensor(graph_ids)
-        if ids.numel() != self.batch_size:
-            raise ValueError(f"ReplayedDualStep was captured for {self.batch_size} graphs per step, got {ids.numel()}")
-        self.graph_ids.copy_(ids.reshape(-1), non_blocking=True)
-        self.r.fill_(float(self._r_of(epoch)))
-        mixed = bool(epoch > self.model.mix_after_epoch)
-        self.graphs[mixed].replay()
-        self._select(mixed)
-        return self.loss
+        for p, g in self._grads[mixed]:          # each graph wrote the gradients into tensors of its own
+            p.grad = g
+        super()._select(mixed)
 
     def overflowed(self) -> bool:
         """True if a step since the last call (or since capture) got a pair that did not fit the capacity.  One host read; clears the flag."""
-        seen = bool(int(self._overflow))
-        self._overflow.zero_()
-        return seen
+        return _take_overflow(self)
 
-    def check_epoch(self, perm) -> None:
-        """Raise ValueError if a full batch of the epoch ``perm`` exceeds the capacity in primal nodes, primal edges (= dual nodes) or dual
-        edges: the totals of every batch are taken on the device and read back once."""
-        ds, B = self.primal_ds, self.batch_size
-        p = torch.as_tensor(perm).to(ds.x_all.device, torch.int64).reshape(-1)
-        full = int(p.numel()) // B
-        if full == 0:
-            return
-        p = p[: full * B].view(full, B)
-        n, e, ed = torch.stack([ds.node_counts[p].sum(1).max(), ds.edge_counts[p].sum(1).max(),
-                                self.dual_ds.edge_counts[p].sum(1).max()]).tolist()
-        if n + 2 > self.capacity[0] or e > self.capacity[1] or ed > self.capacity[2]:
-            raise ValueError(f"a batch of this epoch needs (N, E, E_dual) = ({n} + 2 padding nodes, {e}, {ed}), above the capacity "
-                             f"{self.capacity}")
+
+# ---- the evaluators ---------------------------------------------------------------------------------------------------------------------------
+def _new_logs(ev, count, logits, k, bins, max_graphs, max_edges):
+    """``count`` EpochLogs for the evaluator ``ev``, whose forward gives ``logits``.  ``max_graphs`` / ``max_edges`` default to the
+    dataset's totals."""
+    ds = ev._datasets[0]
+    y_cols = int(ds.y_all.numel() // max(int(ds.y_all.shape[0]), 1))
+    mg = ds.num_graphs if max_graphs is None else int(max_graphs)
+    me = int(ds.edge_local_all.shape[1]) if max_edges is None else int(max_edges)
+    # budget batching may close a batch after any graph: at worst one graph per batch
+    most = mg if ev.ragged else -(-mg // ev.batch_size)
+    return [EpochLog(k, mg, me, max(most, 1), int(logits.shape[1]), y_cols, bins, False, ds.x_all.device) for _ in range(count)]
+
+
+def _loss_triple(loss_dict):
+    return torch.stack([loss_dict[key].reshape(()) for key in ("loss", "pred", "info")]).to(torch.float32)
+
+
+def _reset_logs(ev):
+    for log in (ev.log, getattr(ev, "dual_log", None)):
+        if log is not None:
+            log.reset()
+
+
+def _capture_evaluator(ev, make_logs):
+    """Capture the graphs of the evaluator ``ev`` in eval mode; ``make_logs()`` runs on the side stream ahead of the warm-up.  The logs
+    are empty afterwards."""
+    try:
+        with _capture_mode(ev._model, evaluating=True):
+            ev._warm_up_and_capture(make_logs, lambda: _reset_logs(ev))
+    finally:
+        _reset_logs(ev)
+
+
+def _run_epoch(ev, graph_ids, epoch):
+    """Reset the logs, replay every full batch (ragged: every row of ``batches``), run the tail eagerly in eval mode, compute."""
+    ids = torch.as_tensor(graph_ids).reshape(-1)
+    B, n = ev.batch_size, int(ids.numel())
+    _reset_logs(ev)
+    rows, left = (ev.batches(ids), 0) if ev.ragged else ([ids[s:s + B] for s in range(0, n - B + 1, B)], n % B)
+    for row in rows:
+        ev.step(row, epoch)
+    if left:
+        with _forward_mode(ev._model, True):
+            tail = ids[n - left:].to(ev.graph_ids.device, torch.int64)
+            ev._forward(*[ds.collate(tail) for ds in ev._datasets], epoch)
+    return ev.log.compute()
+
+
+class ReplayedEval(_Replayed):
+    """``ReplayedEval(gsat, dataset, batch_size, k, capacity=None, bins=64, max_graphs=None, max_edges=None)``: an evaluation epoch over
+    ``dataset`` (a PackedDataset with ``edge_label_all``) as replays of ONE captured hipGraph that holds clear_cache, collate_padded,
+    ``gsat.forward_pass(b, 0, False)`` under ``torch.no_grad()`` with every module in ``eval()`` mode, and ``log.append`` into an
+    :class:`~dp_gsat_amd.eval_log.EpochLog` (``log``).  Three warm-up runs on a side stream precede the capture; the modules' training
+    flags, ``sync_free`` and ``sync_loss_dict`` are put back afterwards and the log is reset.  No optimizer is needed.
+
+    The graph reads the parameters and the BatchNorm running statistics where they live, so a replay after ``ReplayedStep.step`` (or an
+    eager optimizer step) scores the new weights.  It writes none of them, draws no noise and no dropout mask, and leaves the device seed
+    stream alone: evaluating between training steps does not change the training run.
+
+    ``max_graphs`` / ``max_edges`` (the log's capacities) default to the dataset's totals; a batch that does not fit ``capacity``, or an
+    append that does not fit the log, is refused on the device and raised by ``run`` / ``log.compute()``; ``check_epoch`` tells beforehand
+    whether an epoch's full batches fit ``capacity``.
+
+    After a step: ``edge_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3] and ``batch`` hold the replay's outputs until the next.
+
+    Refused with ValueError, like the padded path: the multi-label criterion, ``sync_group`` BatchNorm, and ``DualGSAT`` (see
+    ``ReplayedDualEval``).
+
+    ``ragged=True``: as in ``ReplayedStep`` -- ``batch_size`` graph slots, ``step`` takes 1 to ``batch_size`` ids, and ``run`` packs its ids
+    with ``budget_batches`` and replays EVERY batch: there is no eager tail.  The log then has room for one batch per graph."""
+
+    def __init__(self, gsat, dataset, batch_size: int, k: int, capacity: Optional[tuple] = None, bins: int = 64,
+                 max_graphs: Optional[int] = None, max_edges: Optional[int] = None, graph=None, ragged: bool = False):
+        if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
+            raise ValueError("ReplayedEval replays GSAT.forward_pass; the dual/primal evaluation (DualGSAT) is ReplayedDualEval's")
+        if getattr(gsat.criterion, "multi_label", False):
+            raise ValueError(_MULTI_LABEL)
+        _refuse_sync_group(gsat)
+        if dataset.edge_label_all is None or dataset.y_all is None:
+            raise ValueError("ReplayedEval needs a dataset with edge labels and graph labels")
+        self.gsat, self.dataset = gsat, dataset
+        self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
+        self.log = self.batch = self.clf_logits = self.edge_att = self.losses = None
+        sizes = (int(k), int(bins), max_graphs, max_edges)
+        _capture_evaluator(self, lambda: self._make_log(sizes))
+
+    def _make_log(self, sizes):
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        with torch.no_grad():
+            logits = self.gsat.forward_pass(b, 0, False)[3]
+        self.log, = _new_logs(self, 1, logits, *sizes)
+
+    def _forward(self, b, epoch):
+        """Append the eval-mode forward of batch ``b`` to the log; the modules are in eval mode and sync_loss_dict is off."""
+        with torch.no_grad():
+            att, _, ld, logits = self.gsat.forward_pass(b, epoch, False)
+            losses = _loss_triple(ld)
+            att = edge_tensor(att)
+            self.log.append(att, b, logits, losses)
+        return att, logits, losses
+
+    def run_once(self):
+        """The body of the captured graph, run on the current stream."""
+        clear_cache()
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        b.r = self.r
+        att, logits, losses = self._forward(b, 0)
+        self._publish(False, edge_att=att, clf_logits=logits, losses=losses, batch=b)
+
+    def run(self, graph_ids, epoch: int) -> dict:
+        """One evaluation epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, the
+        tail of fewer than ``batch_size`` graphs runs eagerly (``dataset.collate``, the same eval-mode forward, the same append), and
+        ``log.compute()`` -- two host reads -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
+        return _run_epoch(self, graph_ids, epoch)
 
 
 # The (base, counter) states of every ReplayedDualEval: a captured graph holds its state's address in a gsat_seed_next node, so a state
@@ -514,7 +511,7 @@ _EVAL_SEED_STATES = []
 _DUAL_SCORES = ("att_auroc", "precision@{k}", "delta_kl", "avg_signal_att_weights", "avg_bkg_att_weights")
 
 
-class ReplayedDualEval:
+class ReplayedDualEval(_Replayed):
     """``ReplayedDualEval(dual_gsat, primal_ds, dual_ds, batch_size, k, capacity=None, bins=64, max_graphs=None, max_edges=None,
     score_dual=False, seed=None, graphs=None)``: a dual/primal evaluation epoch (``dual_eval_one_batch`` over a dataset and its dual) as
     replays of captured hipGraphs.  One replay holds clear_cache, collate_padded_pair, one gsat_seed_next, ``dual_forward_pass(pb, db,
@@ -535,6 +532,9 @@ class ReplayedDualEval:
     ``score_dual=True``: a second log, ``dual_log``, takes the same primal batches with the dual attention on the primal edge slots in
     place of the primal attention (dual node row k is primal edge slot k), and ``run`` adds its attention scores under a ``dual_`` prefix.
 
+    After a step: ``edge_att`` [E_cap, 1], ``dual_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3], ``batch`` and ``dual_batch``
+    hold the replay's outputs until the next replay of the same graph.
+
     Refused with ValueError before anything is captured: what a padded pair refuses (the multi-label criterion, edge attention,
     ``check_pair``, a capacity that is no triple), ``sync_group`` BatchNorm, a model without ``dual_forward_pass`` and a dataset without
     edge labels or graph labels.  Overflow of the joint capacity sets the log's flag bit 0 and is raised by ``run``; ``check_epoch``
@@ -546,41 +546,40 @@ class ReplayedDualEval:
         m = dual_gsat
         if not hasattr(m, "dual_forward_pass"):
             raise ValueError("ReplayedDualEval replays DualGSAT.dual_forward_pass; ReplayedEval covers a plain GSAT")
-        if any(getattr(mod, "sync_group", None) for mod in m.modules()):
-            raise ValueError("a padded batch cannot take sync_group BatchNorm (its statistics are reduced over ranks on the host's schedule)")
+        _refuse_sync_group(m)
         if primal_ds.edge_label_all is None or primal_ds.y_all is None or dual_ds.y_all is None:
             raise ValueError("ReplayedDualEval needs datasets with edge labels (primal) and graph labels")
-        self.batch_size, self.capacity = _padded_pair_setup(m, primal_ds, dual_ds, batch_size, capacity)
-        self.model, self.primal_ds, self.dual_ds = m, primal_ds, dual_ds
-        dev = primal_ds.x_all.device
-        self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
-        self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
+        _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs)
         if seed is None:        # a fixed mix of torch.initial_seed(): follows torch.manual_seed, draws nothing
             seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & 0x7FFFFFFFFFFFFFFF
         self.base = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.seed_state = torch.empty(2, dtype=torch.int64, device=dev)
+        self.seed_state = torch.empty(2, dtype=torch.int64, device=primal_ds.x_all.device)
         _EVAL_SEED_STATES.append(self.seed_state)
         self._set_seed_state(0)
         self.score_dual = bool(score_dual)
         self.log = self.dual_log = None
         self.batch = self.dual_batch = self.edge_att = self.clf_logits = self.losses = self.dual_att = None
-        unmixed, mixed = graphs if graphs is not None else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
-        self.graphs = {False: unmixed, True: mixed}
-        self._outputs = {}
-        self._capture(int(k), int(bins), max_graphs, max_edges)
-
-    _r_of = ReplayedDualStep._r_of
-    check_epoch = ReplayedDualStep.check_epoch
+        sizes = (int(k), int(bins), max_graphs, max_edges)
+        try:
+            _capture_evaluator(self, lambda: self._make_logs(sizes))
+        finally:
+            self._set_seed_state(0)
 
     def _set_seed_state(self, counter):
         signed = lambda v: v - (1 << 64) if v >= 1 << 63 else v
         self.seed_state.copy_(torch.tensor([signed(self.base), signed(int(counter) & 0xFFFFFFFFFFFFFFFF)], dtype=torch.int64))
 
+    def _make_logs(self, sizes):
+        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
+        with torch.no_grad():
+            logits = self.model.dual_forward_pass(pb, db, 0, False, dual_seed=0)[3]
+        logs = _new_logs(self, 2 if self.score_dual else 1, logits, *sizes)
+        self.log, self.dual_log = logs[0], logs[1] if self.score_dual else None
+
     def _forward(self, pb, db, epoch):
         """Append the eval-mode forward of the pair (padded or not) to the log(s), with the stream's next seed word when noise is drawn;
         the modules are in eval mode and sync_loss_dict is off.  Returns (primal attention, logits, losses, dual attention on the primal
         edges, seed word)."""
-        from ._lib import call, ptr, stream
         m = self.model
         word = None
         if m.gumbel_noise_in_eval:
@@ -591,7 +590,7 @@ class ReplayedDualEval:
         try:
             with torch.no_grad():
                 att, _, ld, logits = m.dual_forward_pass(pb, db, epoch, False, dual_seed=word)
-                losses = torch.stack([ld["loss"].reshape(()), ld["pred"].reshape(()), ld["info"].reshape(())]).to(torch.float32)
+                losses = _loss_triple(ld)
                 att = edge_tensor(att)
                 dual_att = m.dual_att[:att.shape[0]]
                 self.log.append(att, pb, logits, losses)
@@ -603,72 +602,11 @@ class ReplayedDualEval:
 
     def run_once(self, mixed: bool):
         """The body of one captured graph, run on the current stream."""
-        from .collate import collate_padded_pair
         clear_cache()
         pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
         db.r = self.r
-        epoch = self.model.mix_after_epoch + (1 if mixed else 0)           # only the mix reads it: r comes from db.r
-        att, logits, losses, dual_att, word = self._forward(pb, db, epoch)
-        self._outputs[mixed] = dict(batch=pb, dual_batch=db, edge_att=att, clf_logits=logits, losses=losses, dual_att=dual_att, _word=word)
-        self._select(mixed)
-
-    def _select(self, mixed):
-        for key, v in self._outputs[mixed].items():
-            setattr(self, key, v)
-
-    def _capture(self, k, bins, max_graphs, max_edges):
-        from .collate import collate_padded_pair
-        m, ds, dev = self.model, self.primal_ds, self.primal_ds.x_all.device
-        was_sync_free = sync_free()
-        restore = _eval_mode(m)
-        set_sync_free(True)
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                pb, db = collate_padded_pair(ds, self.dual_ds, self.graph_ids, self.capacity)
-                with torch.no_grad():
-                    logit_cols = int(m.dual_forward_pass(pb, db, 0, False, dual_seed=0)[3].shape[1])
-                y_cols = int(ds.y_all.numel() // max(int(ds.y_all.shape[0]), 1))
-                mg = ds.num_graphs if max_graphs is None else int(max_graphs)
-                me = int(ds.edge_local_all.shape[1]) if max_edges is None else int(max_edges)
-                new_log = lambda: EpochLog(k, mg, me, max(-(-mg // self.batch_size), 1), logit_cols, y_cols, bins, False, dev)
-                self.log = new_log()
-                self.dual_log = new_log() if self.score_dual else None
-                for mixed in (False, True, False):          # both bodies run eagerly before either is captured
-                    self.run_once(mixed)
-            torch.cuda.current_stream().wait_stream(side)
-            if int(self.batch.valid[3]) != 0:
-                raise ValueError(f"ReplayedDualEval: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
-            self._reset_logs()
-            for mixed in (False, True):
-                with torch.cuda.graph(self.graphs[mixed]):
-                    self.run_once(mixed)
-        finally:
-            set_sync_free(was_sync_free)
-            restore()
-            clear_cache()
-            self._reset_logs()
-            self._set_seed_state(0)
-
-    def _reset_logs(self):
-        for log in (self.log, self.dual_log):
-            if log is not None:
-                log.reset()
-
-    def step(self, graph_ids, epoch: int) -> None:
-        """Evaluate the graphs ``graph_ids`` (exactly ``batch_size`` ids) at ``epoch`` -- the dual r follows its schedule, the mixed graph runs
-        when ``epoch > mix_after_epoch`` -- with the seed stream's next word, and append them to the log(s); nothing is read back.
-        ``edge_att`` [E_cap, 1], ``dual_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3], ``batch`` and ``dual_batch`` hold the
-        replay's outputs until the next replay of the same graph."""
-        ids = torch.as_tensor(graph_ids)
-        if ids.numel() != self.batch_size:
-            raise ValueError(f"ReplayedDualEval was captured for {self.batch_size} graphs per step, got {ids.numel()}")
-        self.graph_ids.copy_(ids.reshape(-1), non_blocking=True)
-        self.r.fill_(float(self._r_of(epoch)))
-        mixed = bool(epoch > self.model.mix_after_epoch)
-        self.graphs[mixed].replay()
-        self._select(mixed)
+        att, logits, losses, dual_att, word = self._forward(pb, db, _mix_epoch(self.model, mixed))
+        self._publish(mixed, batch=pb, dual_batch=db, edge_att=att, clf_logits=logits, losses=losses, dual_att=dual_att, _word=word)
 
     def run(self, graph_ids, epoch: int) -> dict:
         """One evaluation epoch over ``graph_ids`` (any number, in visiting order) at ``epoch``: the seed stream restarts at (base, epoch <<
@@ -676,20 +614,8 @@ class ReplayedDualEval:
         datasets' ``collate``, the same eval-mode forward with the next seed word, the same appends), and ``log.compute()`` gives the
         scores -- with ``score_dual`` also ``dual_att_auroc``, ``dual_precision@k``, ``dual_delta_kl``, ``dual_avg_signal_att_weights`` and
         ``dual_avg_bkg_att_weights`` of the dual attention."""
-        ids = torch.as_tensor(graph_ids).reshape(-1)
-        B, n = self.batch_size, int(ids.numel())
         self._set_seed_state(int(epoch) << 32)
-        self._reset_logs()
-        for s in range(0, n - B + 1, B):
-            self.step(ids[s:s + B], epoch)
-        if n % B:
-            restore = _eval_mode(self.model)
-            try:
-                tail = ids[n - n % B:].to(self.primal_ds.x_all.device, torch.int64)
-                self._forward(self.primal_ds.collate(tail), self.dual_ds.collate(tail), epoch)
-            finally:
-                restore()
-        res = self.log.compute()
+        res = _run_epoch(self, graph_ids, epoch)
         if self.dual_log is not None:
             dual = self.dual_log.compute()
             for key in _DUAL_SCORES:

@@ -502,4 +502,5 @@ def test_replayed_eval_refusals(dev):
     ev = G.ReplayedEval(gsat, ds, 5, 5)                                       # and the plain model is taken
     with pytest.raises(ValueError, match="captured for 5"):
         ev.step([0, 1, 2], 0)
+    ev.check_epoch(list(range(ds.num_graphs)))                                # inherited: the default capacity takes any batch
     G.clear_cache()
