@@ -36,6 +36,9 @@ static int gemm_rm(hipStream_t stream, bool ta, bool tb, int64_t M, int64_t N, i
                    int64_t ldb, float beta, float* C, int64_t ldc, GemmWs ws = {nullptr, 0}, bool split_ok = false, SlabJob* defer = nullptr) {
     const char* env = getenv("GSAT_ATTN_BWD_SPLIT");                    // read per call: bench.py times both settings in one process
     const bool bwd_split = !(env && atoi(env) == 0);
+    // the weight gradients dh^T x of the backward (A and B both reduction-major): the streaming kernel where its plan says eligible,
+    // else the same gemm_f32 call as below
+    if (ta && !tb && split_ok && bwd_split) return gemm_wgrad(stream, M, N, K, A, lda, B, ldb, C, ldc, beta != 0.f, ws.ptr, ws.floats, defer);
     return gemm_f32(stream, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, nullptr, beta != 0.f, ws.ptr, ws.floats, split_ok && bwd_split, defer);
 }
 
@@ -720,9 +723,10 @@ static int launch_seg_stats(hipStream_t stream, PreAct<EDGE> pre, const int32_t*
 }
 
 // split-K slabs of the weight-gradient GEMMs: dW2, dW1 (edge mode: its two halves).  Each keeps its own region, because their ordered
-// sums are deferred to ONE launch at the end of the backward (slab_reduce_jobs)
-static size_t attn_gemm_ws_w2(const gsat_attn_args* a) { return align_up(gemm_workspace_floats(a->C2, a->C1, a->M, true), 64); }
-static size_t attn_gemm_ws_w1(const gsat_attn_args* a) { return align_up(gemm_workspace_floats(a->C1, a->H, a->N, true), 64); }
+// sums are deferred to ONE launch at the end of the backward (slab_reduce_jobs).  Sized for whichever of the streaming kernel (gemm_rm) and
+// the tile kernel's split (the exact-fp32 leg) needs more
+static size_t attn_gemm_ws_w2(const gsat_attn_args* a) { return align_up(gemm_wgrad_workspace_floats(a->C2, a->C1, a->M), 64); }
+static size_t attn_gemm_ws_w1(const gsat_attn_args* a) { return align_up(gemm_wgrad_workspace_floats(a->C1, a->H, a->N), 64); }
 static size_t attn_gemm_ws_floats(const gsat_attn_args* a) { return attn_gemm_ws_w2(a) + (a->edge_mode ? 2 : 1) * attn_gemm_ws_w1(a); }
 
 static int check_args(const gsat_attn_args* a, const char* who) {

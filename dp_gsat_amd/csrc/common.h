@@ -65,6 +65,12 @@ int gemm_f32(hipStream_t stream, bool a_t, bool b_t, int64_t M, int64_t N, int64
              SlabJob* defer = nullptr);
 int slab_reduce_jobs(hipStream_t stream, const SlabJob* jobs, int n);
 size_t gemm_workspace_floats(int64_t M, int64_t N, int64_t K, bool reduce_rows);
+// streaming split-bf16 weight gradient C[Mo,No] (+)= A^T B, A [K,Mo], B [K,No] (gemm.hip: k_wgrad_x3); the plan is host arithmetic
+struct WgradPlan { int eligible, S, rows; size_t ws_floats; };      // S row ranges of `rows` rows (the last one shorter), [S][Mo][No] workspace
+WgradPlan wgrad_plan(int64_t Mo, int64_t No, int64_t K);
+size_t gemm_wgrad_workspace_floats(int64_t Mo, int64_t No, int64_t K);
+int gemm_wgrad(hipStream_t stream, int64_t Mo, int64_t No, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+               int64_t ldc, bool accumulate, float* ws, size_t ws_floats, SlabJob* defer = nullptr);
 
 // ---- gather-sum over a CSR (aggregate.hip), reused by the extractor backward -------------------------
 int aggr_sum_fwd_impl(hipStream_t stream, const float* x, const float* self_rows, const float* att, const float* edge_emb,

@@ -1069,6 +1069,196 @@ int slab_reduce_jobs(hipStream_t stream, const SlabJob* jobs, int n) {
     return GSAT_OK;
 }
 
+// ================================================================================================================
+// Streaming split-bf16 weight gradient: C[Mo,No] = A^T B with A [K,Mo] and B [K,No] row-major, K = rows of the batch (huge), Mo and No
+// a few hundred (extractor dW2 = dh2^T a1, dW1 = dh1^T emb).  On the tile kernel above these run as ~1.6 short workgroups per CU, each
+// with one slab of loads in flight, two barriers per slab and a 64 KB partial slab per 256 KB read: half the copy rate for their operand
+// bytes.  Here the launch is about ONE 8-wave workgroup per CU: `tiles` 128 x 128 output tiles x S contiguous row ranges.  A workgroup
+// keeps its tile in accumulators for the whole range (wave w: rows 32 (w >> 1), columns 64 (w & 1): two 32 x 32 MFMA tiles) and streams
+// 32-row slabs: the loads of THREE slabs are in flight in registers (waves 0-3 stage A, waves 4-7 stage B: 8 float2 per thread and slab)
+// while a fourth is split into the bf16 hi / lo planes of a double-buffered LDS image (the [k/8][col][8 bf16] image of
+// store_split_kmajor), so a slab costs one barrier.  Loads are issued unconditionally with the row clamped to the range; rows beyond the
+// range are zeroed when the slab is stored to LDS.  Four products per 16 k in the order of k_gemm_bf16x3 (lo*lo, lo*hi, hi*lo, hi*hi),
+// slabs in ascending order, partial tiles to a [S][Mo][No] workspace that the ordered slab sum adds in range order: bitwise
+// reproducible, no atomics.  The column tiles of one row range sit next to each other in the linear tile list (gemm_tile_coords), so
+// they run on one XCD and the second read of the shared A rows is an L2 hit.
+// ================================================================================================================
+constexpr int WG_T = 512, WG_TILE = 128;
+constexpr int WG_PLANE = (GK / 8) * WG_TILE * 16;           // bytes of one bf16 plane of one operand: [4 k-octets][128 cols][8 bf16]
+constexpr int WG_BUF = 4 * WG_PLANE;                        // A_hi | A_lo | B_hi | B_lo
+constexpr int WG_MIN_SLABS = 8;                             // fewest 32-row slabs per range (wgrad_plan)
+
+// (A, B and ws are NOT __restrict__: the barrier's fence then keeps every load on its side of it; with noalias operands the compiler moved
+// the prologue's loads of slabs 1 and 2 behind the first barrier)
+__global__ __launch_bounds__(WG_T) void k_wgrad_x3(const float* A, int64_t lda, const float* B, int64_t ldb, float* ws, int Mo, int No, int K,
+                                                   int rows_per) {
+    constexpr int EP_LD = 36;
+    static_assert(2 * WG_BUF >= 8 * 32 * EP_LD * 4, "epilogue staging must fit in the operand planes");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * WG_BUF];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int bx, by, bz;
+    gemm_tile_coords(bx, by, bz);
+    const int m0 = by * WG_TILE, n0 = bx * WG_TILE;
+    const int kbeg = bz * rows_per, kend = min(K, kbeg + rows_per);          // never empty: S = ceil(K / rows_per)
+    const int nslab = (kend - kbeg + GK - 1) / GK;
+    // ---- staging: work item = 8 k x 2 columns of one operand (load_split_kmajor's), threads 0-255 A, 256-511 B ----
+    const int ts = t & 255, cp = (ts & 63) * 2, k8 = ts >> 6;
+    const bool stage_b = t >= 256;
+    const float* const src = stage_b ? B + n0 + cp : A + m0 + cp;
+    const int64_t ld = stage_b ? ldb : lda;
+    const int plane0 = stage_b ? 2 * WG_PLANE : 0;
+    auto gload = [&](StageKM& s, int slab) {
+        const int kb = kbeg + slab * GK + k8 * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s.v[j] = *reinterpret_cast<const float2*>(src + (size_t)min(kb + j, kend - 1) * ld);
+    };
+    auto lstore = [&](StageKM& s, int slab, unsigned char* buf) {
+        const int kb = kbeg + slab * GK + k8 * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s.v[j] = kb + j < kend ? s.v[j] : make_float2(0.f, 0.f);       // rows beyond the range (NaN padding included)
+        store_split_kmajor<WG_TILE>(s, buf + plane0, buf + plane0 + WG_PLANE, ts);
+    };
+    f32x16 acc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    const int r32 = lane & 31, kh = lane >> 5, wm = wave >> 1, wn = wave & 1;
+    auto compute = [&](const unsigned char* buf) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int ko = (2 * ks + kh) * WG_TILE;
+            const int ao = (ko + wm * 32 + r32) * 16;
+            const bf16x8 ah = *reinterpret_cast<const bf16x8*>(buf + ao);
+            const bf16x8 al = *reinterpret_cast<const bf16x8*>(buf + WG_PLANE + ao);
+            bf16x8 bh[2], bl[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int bo = (ko + wn * 64 + 32 * j + r32) * 16;
+                bh[j] = *reinterpret_cast<const bf16x8*>(buf + 2 * WG_PLANE + bo);
+                bl[j] = *reinterpret_cast<const bf16x8*>(buf + 3 * WG_PLANE + bo);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bl[j], acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[j], acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[j], acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[j], acc[j], 0, 0, 0);
+            }
+        }
+    };
+    // ---- pipeline: while slab i is multiplied out of LDS the loads of slabs i + 1 .. i + 3 are in flight; slab i + 1 is then converted
+    // into the other buffer and its stage registers take the loads of slab i + 4.  Three stage registers in rotation (the loop is
+    // unrolled by three so each keeps its name); slabs past the range load the range's last row again (a cache hit) and store zeros.
+    StageKM s0, s1, s2;
+    gload(s0, 0); gload(s1, 1); gload(s2, 2);
+    lstore(s0, 0, lds);
+    gload(s0, 3);
+    __syncthreads();
+    unsigned char* cur = lds;
+    unsigned char* nxt = lds + WG_BUF;
+    auto step = [&](int i, StageKM& s) {
+        compute(cur);
+        lstore(s, i + 1, nxt);                   // every wave finished reading `nxt` (slab i - 1) before the last barrier
+        gload(s, i + 4);
+        __syncthreads();
+        unsigned char* tmp = cur; cur = nxt; nxt = tmp;
+    };
+    int i = 0;
+    for (; i + 3 <= nslab; i += 3) {             // no exit inside a round: a load that an exit leaves unused is sunk behind it, out of flight
+        step(i, s1);
+        step(i + 1, s2);
+        step(i + 2, s0);
+    }
+    if (i < nslab) {                             // one or two slabs left: slab i is in `cur`, slab i + 1 in s1; nothing more to load
+        compute(cur);
+        if (i + 1 < nslab) {
+            lstore(s1, i + 1, nxt);
+            __syncthreads();
+            compute(nxt);
+        }
+        __syncthreads();
+    }
+    // ---- epilogue: the tile kernels' (32 x 32 patch per wave through LDS, 16-byte row stores) into this range's slab ----
+    float* const Cb = ws + (size_t)bz * Mo * No;
+    float* const patch = reinterpret_cast<float*>(lds) + wave * (32 * EP_LD);      // all waves passed the loop's final barrier
+    const int prow = lane >> 3, pcol = (lane & 7) * 4;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * kh) * EP_LD + r32] = acc[j][r];
+        __builtin_amdgcn_wave_barrier();
+        const int col = n0 + wn * 64 + j * 32 + pcol;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int rr = prow + 8 * p;
+            st4(Cb + (size_t)(m0 + wm * 32 + rr) * No + col, ld4(patch + rr * EP_LD + pcol));
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// CUs of the current device, asked once (256 on an MI355X, which is also the answer where no device is present: the plan is host arithmetic)
+static int device_cus() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) {
+            (void)hipGetLastError();
+            v = 256;
+        }
+        return v;
+    }();
+    return n;
+}
+
+// Every decision of gemm_wgrad() for one product; the workspace queries and gsat_gemm_wgrad_plan() run on the same function.
+// Eligible: whole 128 x 128 tiles, a product the split-bf16 rule wants (use_bf16x3), at least two ranges, and WG_MIN_SLABS slabs in every
+// range.  The minimum rests on the bytes a range adds to its operands: a 64 KB partial tile written and read again by the slab sum
+// against 32 KB of operands per slab, so at 8 slabs the partials add at most 2 x 64 / 256 = 1/2 to the traffic (the ratio the tile
+// kernel's split rule accepts: gemm_splits, 8 slabs per split), and the three-slab prologue is amortised over the range.
+// Not eligible: S, rows and the workspace are those of the tile kernel, which gemm_wgrad() then runs.
+WgradPlan wgrad_plan(int64_t Mo, int64_t No, int64_t K) {
+    WgradPlan p{};
+    if (Mo <= 0 || No <= 0 || K <= 0) return p;
+    p.S = gemm_splits(Mo, No, K, true);
+    p.rows = (int)std::min<int64_t>(ceil_div(ceil_div(K, p.S), GK) * GK, INT32_MAX);
+    p.ws_floats = gemm_workspace_floats(Mo, No, K, true);
+    if (Mo % WG_TILE != 0 || No % WG_TILE != 0 || K >= (1ll << 31) - 8 * GK || !use_bf16x3(Mo, No, K, true)) return p;
+    const int64_t tiles = (Mo / WG_TILE) * (No / WG_TILE), s0 = device_cus() / tiles;
+    if (s0 < 2 || K < s0 * WG_MIN_SLABS * GK) return p;
+    const int64_t rows = ceil_div(ceil_div(K, s0), GK) * GK;          // whole slabs per range; the last range takes what is left
+    p.eligible = 1;
+    p.rows = (int)rows;
+    p.S = (int)ceil_div(K, rows);
+    p.ws_floats = (size_t)p.S * Mo * No;
+    return p;
+}
+
+// workspace that serves gemm_wgrad() AND the tile kernel's split (the exact-fp32 leg of the same caller)
+size_t gemm_wgrad_workspace_floats(int64_t Mo, int64_t No, int64_t K) {
+    return std::max(wgrad_plan(Mo, No, K).ws_floats, gemm_workspace_floats(Mo, No, K, true));
+}
+
+// C[Mo,No] (+)= A^T B on the streaming kernel when wgrad_plan() says eligible, else on gemm_f32 (a_t, split-bf16 allowed).  `defer` as in
+// gemm_f32: the ordered sum of the partial tiles is left to the caller's slab_reduce_jobs.
+int gemm_wgrad(hipStream_t stream, int64_t Mo, int64_t No, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+               int64_t ldc, bool accumulate, float* ws, size_t ws_floats, SlabJob* defer) {
+    const WgradPlan p = wgrad_plan(Mo, No, K);
+    if (!p.eligible) return gemm_f32(stream, true, false, Mo, No, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, ws, ws_floats, true, defer);
+    if (defer) defer->nslab = 0;
+    xcd_switch_once();
+    GSAT_REQUIRE(A && B && C && lda >= Mo && ldb >= No && ldc >= No && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0, GSAT_ERR_ARG, "gemm_wgrad: bad argument");
+    GSAT_REQUIRE(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0) && ((uintptr_t)ws % 16 == 0), GSAT_ERR_ARG,
+                 "gemm_wgrad: operands, output and workspace must be 16-byte aligned");
+    GSAT_REQUIRE(ws && ws_floats >= p.ws_floats, GSAT_ERR_WORKSPACE, "gemm_wgrad: workspace too small");
+    const dim3 grid((unsigned)(No / WG_TILE), (unsigned)(Mo / WG_TILE), (unsigned)p.S);
+    k_wgrad_x3<<<grid, WG_T, 0, stream>>>(A, lda, B, ldb, ws, (int)Mo, (int)No, (int)K, p.rows);
+    GSAT_LAUNCH_CHECK();
+    const SlabJob job{ws, p.S, (size_t)Mo * No, (int)Mo, (int)No, ldc, accumulate ? 1 : 0, C};
+    if (defer) { *defer = job; return GSAT_OK; }
+    return slab_reduce_jobs(stream, &job, 1);
+}
+
 // post_nn of PNAConvSimple on the virtual aggregate: out [N, Ho] = Agg W^T + b (forward) and dW [Ho, NAGG*2*H] = dOut^T Agg (split over
 // the rows, slabs summed in order), both on the split-bf16 tile kernel with the operand loader that recomputes the x_i columns.
 int pna_post_fwd(hipStream_t stream, const PnaVirt& pv, int64_t Nrows, const float* W, int64_t ldw, const float* bias, int64_t Ho, float* out, int64_t ldo) {
@@ -1163,6 +1353,22 @@ int gsat_gemm_bf16x3(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const fl
 }
 
 size_t gsat_gemm_workspace_floats(int a_t, int64_t M, int64_t N, int64_t K) { return gemm_workspace_floats(M, N, K, a_t != 0); }
+
+/* (eligible, S, rows per range, workspace floats) of gsat_gemm_wgrad_x3 for these extents; see include/gsat_hip.h */
+int gsat_gemm_wgrad_plan(int64_t Mo, int64_t No, int64_t K, int32_t* plan) {
+    GSAT_REQUIRE(plan && Mo > 0 && No > 0 && K > 0, GSAT_ERR_ARG, "gsat_gemm_wgrad_plan: bad argument");
+    const WgradPlan p = wgrad_plan(Mo, No, K);
+    GSAT_REQUIRE(p.ws_floats <= (size_t)INT32_MAX, GSAT_ERR_UNSUPPORTED, "gsat_gemm_wgrad_plan: workspace of %zu floats does not fit int32", p.ws_floats);
+    const int32_t v[4] = {p.eligible, p.S, p.rows, (int32_t)p.ws_floats};
+    memcpy(plan, v, sizeof(v));
+    return GSAT_OK;
+}
+
+/* C[Mo,No] = (accumulate ? C : 0) + A^T B, its ordered slab sum included; see include/gsat_hip.h */
+int gsat_gemm_wgrad_x3(int64_t Mo, int64_t No, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
+                       int accumulate, float* workspace, size_t workspace_floats, void* stream) {
+    return gemm_wgrad((hipStream_t)stream, Mo, No, K, A, lda, B, ldb, C, ldc, accumulate != 0, workspace, workspace_floats);
+}
 
 /* the dispatch decisions of gsat_gemm_f32 (allow_split == 0) / gsat_gemm_bf16x3 for these arguments; see include/gsat_hip.h */
 int gsat_gemm_plan(int allow_split, int a_t, int b_t, int64_t M, int64_t N, int64_t K, int has_bias, int accumulate, int64_t ldb, int32_t* plan) {

@@ -431,6 +431,20 @@ int gsat_gemm_f32(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const float
 int gsat_gemm_bf16x3(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                      const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int accumulate,
                      float* workspace, size_t workspace_floats, void* stream);
+/*
+ * Weight gradient C[Mo,No] = (accumulate ? C : 0) + A^T B with A [K,Mo] and B [K,No] row-major (K = rows of the batch), split-bf16 as
+ * above.  Large products on whole 128 x 128 tiles run on a streaming kernel: about one workgroup per CU, each holding one output tile
+ * over a contiguous range of rows, partial tiles summed in range order (bitwise reproducible; the last bits differ from
+ * gsat_gemm_bf16x3(a_t = 1), whose split points lie elsewhere).  Every other product runs as gsat_gemm_bf16x3(a_t = 1, b_t = 0).
+ * gsat_gemm_wgrad_plan (host arithmetic, no launch) writes HOST int32[4]:
+ *   [0] 1 = streaming kernel, 0 = the gsat_gemm_bf16x3 path    [1] S, the number of row ranges (K splits)
+ *   [2] rows per range (a multiple of 32; the last range holds the rest)
+ *   [3] workspace floats the call needs (streaming kernel: S * Mo * No)
+ * The workspace must be 16-byte aligned, like A, B and C; lda, ldb, ldc multiples of 4.
+ */
+int gsat_gemm_wgrad_plan(int64_t Mo, int64_t No, int64_t K, int32_t* plan);
+int gsat_gemm_wgrad_x3(int64_t Mo, int64_t No, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
+                       float* C, int64_t ldc, int accumulate, float* workspace, size_t workspace_floats, void* stream);
 
 /* =============================== attention extractor MLP ===================================== */
 
