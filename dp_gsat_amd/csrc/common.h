@@ -138,6 +138,12 @@ __device__ __forceinline__ void st4_nt(float* p, float4 v) {
 __device__ __forceinline__ float4 ld4_off(const float* base, uint32_t byte_off) {
     return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + byte_off);
 }
+// the same, non-temporal: for rows that are read once and should not displace lines that are read again
+__device__ __forceinline__ float4 ld4_off_nt(const float* base, uint32_t byte_off) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(reinterpret_cast<const char*>(base) + byte_off));
+    return make_float4(t.x, t.y, t.z, t.w);
+}
 __device__ __forceinline__ void st4_off(float* base, uint32_t byte_off, float4 v) {
     *reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
@@ -150,6 +156,12 @@ __device__ __forceinline__ void st4_lds(float4* p, float4 v) {
 }
 __device__ __forceinline__ void st1_lds(float* p, float v) { *(__attribute__((address_space(3))) float*)p = v; }
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+// c ? a : b per component, on VALUES: `c ? a.x : b.x` on two lvalues is itself an lvalue, i.e. a load through a selected pointer,
+// which keeps both operands in memory (scratch)
+__device__ __forceinline__ float f1sel(bool c, float a, float b) { return c ? a : b; }
+__device__ __forceinline__ float4 f4sel(bool c, float4 a, float4 b) {
+    return make_float4(f1sel(c, a.x, b.x), f1sel(c, a.y, b.y), f1sel(c, a.z, b.z), f1sel(c, a.w, b.w));
+}
 __device__ __forceinline__ float4 f4fma(float a, float4 x, float4 acc) {
     acc.x = fmaf(a, x.x, acc.x); acc.y = fmaf(a, x.y, acc.y);
     acc.z = fmaf(a, x.z, acc.z); acc.w = fmaf(a, x.w, acc.w);

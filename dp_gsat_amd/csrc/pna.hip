@@ -651,14 +651,23 @@ __global__ __launch_bounds__(PNA_BLOCK, HAS_EE ? 2 : 4) void k_pna_bwd_dst(
 //   trip 2  the window's indices -> LDS, and each lane group's first upstream gradient row -> registers
 //   trip 3  the gathered x_j row of every edge -> LDS by LDS-DMA with a per-lane source address, and the attention of every edge
 //   rows    a lane group per destination row: statistics and first-occurrence args from LDS; as soon as the fold has consumed the
-//           gradient row the next one is requested into the same registers; the per-edge gradient row is written IN PLACE over
-//           the gathered row in LDS; dx_self -> dx, except for the lane group's LAST row, which stays in registers
-//   sums    a lane group per source row, the same thread <-> row map as above: dx[j] = dx_self (read back for the earlier rows, whose
-//           store the later rows have long covered; from the registers for the last one, whose store-then-load nothing would hide)
-//           + dx_add + its edges' rows in by-source slot order, indices and rows straight from LDS: the one write of dx[j]
+//           gradient row the next one is requested into the same registers (non-temporal: read once, it must not displace the
+//           x / dx rows the window reads again); the per-edge gradient row is written IN PLACE over the gathered row in LDS;
+//           dx_self stays in registers for the lane group's LAST K rows (pna_tile_keep: 3, or 2) and goes to dx for the earlier ones
+//           (at C3: 5 % of the rows); after the last row, still ahead of the barrier, the group requests what the sums read from
+//           memory for its first TILE_PREFETCH rows: the stored dx rows, dx_add, d node_att of the accumulate mode
+//   sums    a lane group per source row, the same thread <-> row map as above: dx[j] = dx_self (kept or prefetched, by a select)
+//           + dx_add + its edges' rows in by-source slot order, indices and rows straight from LDS: the one write of dx[j].  The
+//           common path holds LDS reads and stores only; rows beyond TILE_PREFETCH (LDS budgets above the default) load in the loop
 // Edges whose source lies outside the window (or beyond the LDS edge capacity: hub rows) spill their row to dmsg and are
 // added by k_pna_bwd_spill afterwards, in by-source slot order as well, so the result is bitwise reproducible.
 constexpr int TILE_BLOCK = 512;
+// Rows per lane group whose per-source-pass loads are requested ahead of the barrier.  At the default LDS budget (gsat_pna_tile_plan)
+// a window holds at most ceil(rows_cap / GPB) rows per group: 4 / 5 / 5 / 5 / 5 / 4 for LPR 4 / 8 / 16 / 20 / 32 / 64.
+constexpr int TILE_PREFETCH = 5;
+// K: how many of a lane group's last dx_self rows stay in registers (4 VGPRs each).  3 wherever the instantiation then has no
+// scratch, no spilled VGPR and at most 128 VGPRs, else the largest smaller K (measured: see the table in profiles/pna_bwd_dx_keep.md).
+constexpr int pna_tile_keep(int lpr, int nagg, bool natt) { return (lpr == 20 && nagg == 5 && natt) ? 2 : 3; }
 
 // desc[t] = (first row of window t, rowptr_dst[row], rowptr_src[row], 0); desc[T] closes the last window
 __global__ void k_pna_tiles(const int32_t* __restrict__ node_ptr, const int32_t* __restrict__ node_seg, const int32_t* __restrict__ rowptr,
@@ -730,7 +739,7 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
     for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = f4zero();
     if (r < nr && on) {
 #pragma unroll
-        for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4_off(gwin, r * gb + sg * hb + cb);
+        for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4_off_nt(gwin, r * gb + sg * hb + cb);
         xi_cur = ld4_off(xwin, r * hb + cb);
     }
     for (int i = tid; i <= nr; i += TILE_BLOCK) {
@@ -761,7 +770,11 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // ---- destination rows ----------------------------------------------------------------------------------
-    float4 dx_keep = f4zero();                                   // dx_self of the lane group's LAST row: it never leaves the registers
+    constexpr int K = pna_tile_keep(LPR, NAGG, NATT);
+    static_assert(K >= 1 && K <= 3 && K < TILE_PREFETCH, "k_pna_bwd_tile keeps one to three rows");
+    // dx_self of the lane group's LAST K rows, keep<q> the one with q rows of the group after it: they never leave the registers
+    // (named registers, not an array: nothing here may be indexed at run time)
+    float4 keep0 = f4zero(), keep1 = f4zero(), keep2 = f4zero();
     for (; r < nr; r += GPB) {
         const int nr_ = r + GPB;                                 // the lane group's next row
         const int beg = s_rp[r], end = s_rp[r + 1];
@@ -838,9 +851,12 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
             GSAT_TSELF(x) GSAT_TSELF(y) GSAT_TSELF(z) GSAT_TSELF(w)
 #undef GSAT_TSELF
             if (end == beg) dxi = f4zero();                      // amin/amax are +-inf on an empty row: no in-edges, no gradient
-            // earlier rows wait in dx for the per-source pass (the store is long done by then); the last row, whose round trip through
-            // memory nothing would hide, stays in registers
-            if (nr_ < nr) st4_off(dxwin, r * hb + cb, dxi); else dx_keep = dxi;
+            // a row with K or more rows of its group still to come waits in dx for the per-source pass; the last K stay in registers:
+            // every row moves the kept ones up by one, so that keep[q] ends as the row with q rows after it
+            if (r + K * GPB < nr) st4_off(dxwin, r * hb + cb, dxi);
+            if (K > 2) keep2 = keep1;
+            if (K > 1) keep1 = keep0;
+            keep0 = dxi;
         }
         // the x_j half is folded after the self part, so that the self part's coefficients are dead by then; the gradient row is
         // consumed: request the next one into the same registers, in flight under the rest of this row
@@ -848,7 +864,7 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
 #undef GSAT_TFOLD
         if (nr_ < nr && on) {
 #pragma unroll
-            for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4_off(gwin, nr_ * gb + sg * hb + cb);
+            for (int sg = 0; sg < NSEG; ++sg) dcur[sg] = ld4_off_nt(gwin, nr_ * gb + sg * hb + cb);
             xi_cur = ld4_off(xwin, nr_ * hb + cb);
         }
         // pass 2: per-edge gradient rows, in place over the gathered rows
@@ -891,19 +907,50 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
         }
         if (NATT && datt && lane == 0) s_dna[r] = dna_acc;
     }
-    __syncthreads();
-    // ---- per-source sums over the rows kept in LDS (same lane group <-> row map as above: dx[j] is this thread's own store) ----
+    // ---- what the per-source pass reads from memory, requested AHEAD of the barrier into registers the row loop has freed ----------
+    // The pass keeps the lane group <-> row map of the row loop: row i of a group is jg + i * GPB, and a stored dx row is this thread's
+    // own earlier store (program order covers it).  The first PF rows of a group (all of them at the default LDS budget, whatever
+    // LPR) get unconditional loads with the row clamped into the window, masked when they are used; rows beyond load in the loop.
+    // A dx row that was not stored is not requested (its lines would come from HBM for nothing): the window's last row stands in.
+    constexpr int PF = TILE_PREFETCH;
     const float* awin = dx_add ? dx_add + (size_t)n0 * H : nullptr;
-    for (int j = lg.grp >= 0 ? grp : nr; j < nr; j += GPB) {
-        if (!on) continue;
-        const int sb = s_rps[j], se = s_rps[j + 1];
-        float4 acc = j + GPB < nr ? ld4_off(dxwin, j * hb + cb) : dx_keep;
-        // NATT, datt_acc: d node_att is shared by every layer that used the attention: this launch adds its share to what is there
-        const float dprev = (NATT && datt && datt_acc && lane == 0) ? datt[n0 + j] : 0.f;
-        if (awin) {                // a gradient that reaches x by another path (the layer's residual): added here instead of by a separate kernel
-            const float4 ra = ld4_off(awin, j * hb + cb);
-            acc.x += ra.x; acc.y += ra.y; acc.z += ra.z; acc.w += ra.w;
+    // NATT, datt_acc: d node_att is shared by every layer that used the attention: this launch adds its share to what is there
+    const bool want_prev = NATT && datt && datt_acc;
+    const int jg = lg.grp >= 0 ? grp : nr;
+    const int cnt = jg < nr ? (nr - 1 - jg) / GPB + 1 : 0;       // rows of this lane group
+    float4 pdx[PF], padd[PF];
+    float pprev[PF];
+#pragma unroll
+    for (int i = 0; i < PF; ++i) {
+        pdx[i] = f4zero();
+        padd[i] = f4zero();
+        pprev[i] = 0.f;
+    }
+    if (on) {
+#pragma unroll
+        for (int i = 0; i < PF; ++i) pdx[i] = ld4_off(dxwin, (i + K < cnt ? jg + i * GPB : nr - 1) * hb + cb);
+        if (awin) {
+#pragma unroll
+            for (int i = 0; i < PF; ++i) padd[i] = ld4_off(awin, min(jg + i * GPB, nr - 1) * hb + cb);
         }
+        if (want_prev) {
+#pragma unroll
+            for (int i = 0; i < PF; ++i) pprev[i] = datt[n0 + min(jg + i * GPB, nr - 1)];
+        }
+    }
+    __syncthreads();
+    // ---- per-source sums over the rows kept in LDS: dx[j] = (dx_self + dx_add) + its edges' rows in by-source slot order ----------
+    if (!on) return;
+    auto kept = [&](int rem) {                                   // dx_self of the row with `rem` < K rows of its group after it
+        float4 v = keep0;                                        // selects per component: a conditional copy of the whole float4 becomes a
+        if (K > 1) v = f4sel(rem == 1, keep1, v);                // load through a selected POINTER, and the rows then live in scratch
+        if (K > 2) v = f4sel(rem == 2, keep2, v);
+        return v;
+    };
+    // acc: dx_self; ra: a gradient that reaches x by another path (the layer's residual), added here instead of by a separate kernel
+    auto sums = [&](int j, float4 acc, float4 ra, float dprev) {
+        const int sb = s_rps[j], se = s_rps[j + 1];
+        if (awin) { acc.x += ra.x; acc.y += ra.y; acc.z += ra.z; acc.w += ra.w; }
         float sw = 0.f;
         for (int s_ = sb; s_ < se; ++s_) {
             const int kl = s_ < nsl ? s_slot[s_] : slot_map[s0 + s_] - k0;
@@ -915,6 +962,23 @@ __global__ __launch_bounds__(TILE_BLOCK, 4) void k_pna_bwd_tile(
         }
         st4_off(dxwin, j * hb + cb, acc);
         if (NATT && datt && lane == 0) datt[n0 + j] = (s_dna[j] + sw) + dprev;      // destination share (this lane's own LDS store of the row loop) + source share
+    };
+    auto prefetched = [&](auto I) {                              // row I of the lane group, I a compile-time index; false: the group has no such row
+        constexpr int i = decltype(I)::value;
+        const int j = jg + i * GPB, rem = cnt - 1 - i;
+        if (j >= nr) return false;
+        sums(j, f4sel(rem >= K, pdx[i], kept(rem)), padd[i], (want_prev && lane == 0) ? pprev[i] : 0.f);
+        return true;
+    };
+    static_assert(PF == 5, "one call per prefetched row");
+    using std::integral_constant;
+    if (!(prefetched(integral_constant<int, 0>{}) && prefetched(integral_constant<int, 1>{}) && prefetched(integral_constant<int, 2>{}) &&
+          prefetched(integral_constant<int, 3>{}) && prefetched(integral_constant<int, 4>{})))
+        return;
+    for (int j = jg + PF * GPB, rem = cnt - 1 - PF; j < nr; j += GPB, --rem) {       // more than PF rows: a larger LDS budget than the default
+        const float4 acc = rem >= K ? ld4_off(dxwin, j * hb + cb) : kept(rem);
+        const float4 ra = awin ? ld4_off(awin, j * hb + cb) : f4zero();
+        sums(j, acc, ra, (want_prev && lane == 0) ? datt[n0 + j] : 0.f);
     }
 }
 
