@@ -102,6 +102,7 @@ SIGNATURES = {
     "gsat_criterion_block_items": (I64, [I64, INT]),
     "gsat_criterion_max_blocks": (I64, []),
     "gsat_ragged_scan": (INT, [P, I64, P, P, I64, P, P, P, P, P, P]),
+    "gsat_ragged_pair_scan": (INT, [P, I64, P, P, P, I64, I64, I64, I64, P, P, P, P, P, P, P]),
     "gsat_collate_padded_ragged": (INT, [P, I64, P, P, P, P, I64, P, P, I64, I64, P, P, P, P, P, P]),
     "gsat_collate_padded": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P, P]),
     "gsat_collate": (INT, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, P, P, P]),

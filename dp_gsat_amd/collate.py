@@ -89,7 +89,7 @@ class PackedDataset:
             self._capacities[k] = (int(n) + 2, int(e))
         return self._capacities[k]
 
-    def budget_batches(self, perm, capacity: tuple, max_graphs: int) -> torch.Tensor:
+    def budget_batches(self, perm, capacity: tuple, max_graphs: int, dual: Optional["PackedDataset"] = None) -> torch.Tensor:
         """The graphs ``perm`` (ids in visiting order) packed into batches of a node / edge budget, PyG's ``DynamicBatchSampler``: int64
         [num_batches, max_graphs] on the device, one row per batch -- ``collate_padded(row, capacity, ragged=True)`` -- with -1 in the
         unused slots.  In ``perm``'s order a graph opens a new batch when adding it would break ``nodes + 2 <= N_cap``, ``edges <=
@@ -97,28 +97,44 @@ class PackedDataset:
         graph.  A graph that fits no batch alone raises ValueError.
 
         Host work: two cumulative sums over ``perm`` and three searches per batch, on a host copy of the graphs' sizes that is made the
-        first time (this dataset's only host read here)."""
+        first time (this dataset's only host read here).
+
+        ``dual`` (this dataset's dual, ``check_pair`` runs first): the rows for ``collate_padded_pair(self, dual, row, capacity,
+        ragged=True)``.  ``capacity`` is then ``(N_cap, E_cap, E_dual_cap)`` and ``dual_edges <= E_dual_cap`` is a third budget: a third
+        cumulative sum and a fourth search per batch, on a host copy of the dual's edge counts that is made once."""
+        if dual is not None:
+            self.check_pair(dual)
+            if len(capacity) != 3:
+                raise ValueError("budget_batches: with a dual the capacity is (N_cap, E_cap, E_dual_cap)")
         N_cap, E_cap, slots = int(capacity[0]), int(capacity[1]), int(max_graphs)
         if slots < 1:
             raise ValueError("budget_batches needs at least one graph slot per batch")
         if self._host_counts is None:
             both = torch.stack([self.node_counts, self.edge_counts]).cpu().numpy()
             self._host_counts = (both[0].copy(), both[1].copy())
+        if dual is not None and dual._host_counts is None:
+            both = torch.stack([dual.node_counts, dual.edge_counts]).cpu().numpy()
+            dual._host_counts = (both[0].copy(), both[1].copy())
         import numpy as np
         p = torch.as_tensor(perm).reshape(-1).cpu().numpy().astype(np.int64)
         if p.size and (p.min() < 0 or p.max() >= self.num_graphs):
             raise ValueError("budget_batches: graph ids must lie in [0, num_graphs)")
-        cn = np.concatenate([[0], np.cumsum(self._host_counts[0][p])])
-        ce = np.concatenate([[0], np.cumsum(self._host_counts[1][p])])
+        # (running totals over perm, budget) of every size a batch is limited in
+        sums = [(self._host_counts[0], N_cap - 2), (self._host_counts[1], E_cap)]
+        if dual is not None:
+            sums.append((dual._host_counts[1], int(capacity[2])))
+        sums = [(np.concatenate([[0], np.cumsum(c[p])]), room) for c, room in sums]
         starts, s, n = [], 0, int(p.size)
         while s < n:
             # the first position whose running total exceeds the budget ends the batch (side="right": equality still fits)
-            end = min(int(np.searchsorted(cn, cn[s] + N_cap - 2, side="right")) - 1, int(np.searchsorted(ce, ce[s] + E_cap, side="right")) - 1,
-                      s + slots, n)
+            end = min([int(np.searchsorted(c, c[s] + room, side="right")) - 1 for c, room in sums] + [s + slots, n])
             if end <= s:
                 g = int(p[s])
-                raise ValueError(f"budget_batches: graph {g} ({int(self._host_counts[0][g])} nodes + 2 padding nodes, "
-                                 f"{int(self._host_counts[1][g])} edges) does not fit the capacity (N_cap, E_cap) = ({N_cap}, {E_cap})")
+                size = f"{int(self._host_counts[0][g])} nodes + 2 padding nodes, {int(self._host_counts[1][g])} edges"
+                if dual is None:
+                    raise ValueError(f"budget_batches: graph {g} ({size}) does not fit the capacity (N_cap, E_cap) = ({N_cap}, {E_cap})")
+                raise ValueError(f"budget_batches: graph {g} ({size}, {int(dual._host_counts[1][g])} dual edges) does not fit the capacity "
+                                 f"(N_cap, E_cap, E_dual_cap) = ({N_cap}, {E_cap}, {int(capacity[2])})")
             starts.append(s)
             s = end
         starts = np.asarray(starts + [n], dtype=np.int64)
@@ -192,10 +208,12 @@ class PackedDataset:
         ``valid == (0, 0, 0, 1)``.  The batch carries ``ragged = True``."""
         return self._collate_padded(graph_ids, capacity, ragged=bool(ragged))
 
-    def _collate_padded(self, graph_ids, capacity, spoil=None, check=True, ragged=False) -> PaddedBatch:
+    def _collate_padded(self, graph_ids, capacity, spoil=None, check=True, ragged=False, scan=None) -> PaddedBatch:
         """``collate_padded``; ``spoil`` (a 0-dim bool on the device) makes the batch an overflow whatever its size -- the joint verdict of a
-        pair: the node total handed to the kernel is raised by the capacity, which fails its ``N + 2 <= N_cap`` test, and an overflow
-        batch reads neither scan.  ``check=False`` leaves the host read of the overflow word to the caller."""
+        fixed-count pair: the node total handed to the kernel is raised by the capacity, which fails its ``N + 2 <= N_cap`` test, and an
+        overflow batch reads neither scan.  ``check=False`` leaves the host read of the overflow word to the caller.  ``scan`` (ragged
+        only): ``(out_node_ptr, out_edge_ptr, state, safe_ids, empty)`` made by the caller -- ``gsat_ragged_pair_scan``'s, whose state
+        carries the joint verdict of a ragged pair -- in place of this batch's own ``gsat_ragged_scan``."""
         from .graph_index import sync_free
         ids = graph_ids.to(self.x_all.device, torch.int64).contiguous()
         B, dev = int(ids.shape[0]), ids.device
@@ -207,12 +225,15 @@ class PackedDataset:
             # one launch: both scans with the empty slots counting nothing (the collation kernel gives them no row and never looks their
             # id up), the number of filled slots, and whether a filled slot sits behind an empty one -- the verdict stays on the device
             if spoil is not None:
-                raise ValueError("a ragged batch takes no joint overflow verdict (collate_padded_pair is not ragged)")
-            out_node_ptr, out_edge_ptr = (torch.empty(B + 1, dtype=torch.int64, device=dev) for _ in range(2))
-            state, safe = torch.empty(2, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
-            empty = torch.empty(B, dtype=torch.bool, device=dev)
-            call("gsat_ragged_scan", ptr(ids), B, ptr(self.node_ptr_all), ptr(self.edge_ptr_all), self.num_graphs, ptr(out_node_ptr),
-                 ptr(out_edge_ptr), ptr(state), ptr(safe), ptr(empty), stream())
+                raise ValueError("a ragged batch takes no torch-made overflow verdict (a ragged pair's is in its scan's state)")
+            if scan is not None:
+                out_node_ptr, out_edge_ptr, state, safe, empty = scan
+            else:
+                out_node_ptr, out_edge_ptr = (torch.empty(B + 1, dtype=torch.int64, device=dev) for _ in range(2))
+                state, safe = torch.empty(2, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+                empty = torch.empty(B, dtype=torch.bool, device=dev)
+                call("gsat_ragged_scan", ptr(ids), B, ptr(self.node_ptr_all), ptr(self.edge_ptr_all), self.num_graphs, ptr(out_node_ptr),
+                     ptr(out_edge_ptr), ptr(state), ptr(safe), ptr(empty), stream())
             ids = safe
         else:
             zero = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -249,7 +270,8 @@ class PackedDataset:
                            num_graphs=B + 1, valid=valid, capacity=(N_cap, E_cap), node_src_row=node_src, edge_src_slot=edge_src, **extra)
 
 
-def collate_padded_pair(primal: PackedDataset, dual: PackedDataset, graph_ids: torch.Tensor, capacity: Optional[tuple] = None):
+def collate_padded_pair(primal: PackedDataset, dual: PackedDataset, graph_ids: torch.Tensor, capacity: Optional[tuple] = None,
+                        ragged: bool = False):
     """``(pb, db)``: the graphs ``graph_ids`` of a dataset and of its dual (``primal.line_graph_dataset()``) as fixed-capacity batches that
     line up -- ``pb = primal.collate_padded(ids, (N_cap, E_cap))`` and ``db = dual.collate_padded(ids, (E_cap + 2, E_dual_cap))``, so dual
     node row k < E_cap is primal edge slot k (the + 2: the padding nodes every padded batch keeps).  ``capacity = (N_cap, E_cap,
@@ -257,17 +279,37 @@ def collate_padded_pair(primal: PackedDataset, dual: PackedDataset, graph_ids: t
     ``DualGSAT.dual_forward_pass`` takes padded batches only as such a pair.
 
     Overflow is joint and decided on the device: if either batch does not fit, BOTH are all padding with ``valid[3] == 1`` (ValueError
-    outside sync-free mode, after one host read)."""
+    outside sync-free mode, after one host read).
+
+    ``ragged=True``: ``graph_ids`` are ``B`` graph slots with the empty ones (negative ids) trailing, as in ``collate_padded(...,
+    ragged=True)``; both batches carry ``ragged = True``, ``num_graphs = B + 1`` and zero ``y`` rows in the empty slots, and ``pb.valid ==
+    (N, E, b, 0)``, ``db.valid == (E, E_dual, b, 0)`` with ``b`` the filled slots, counted on the device.  ONE launch
+    (``gsat_ragged_pair_scan``) makes the three scans and the joint verdict -- a budget exceeded, a filled slot behind an empty one, an id
+    that is not below the dataset's graph count -- and both collations read it: an overflow pair is all padding with ``valid == (0, 0,
+    0, 1)`` on both sides.  Nothing depends on the batch from the host."""
     from .graph_index import sync_free
     primal.check_pair(dual)
     ids = torch.as_tensor(graph_ids).to(primal.x_all.device, torch.int64).contiguous()
     if capacity is None:
         capacity = primal.pair_capacity_for(dual, int(ids.shape[0]))
     N_cap, E_cap, Ed_cap = (int(c) for c in capacity)
-    n, e, ed = primal.node_counts[ids].sum(), primal.edge_counts[ids].sum(), dual.edge_counts[ids].sum()
-    spoil = (n + 2 > N_cap) | (e > E_cap) | (ed > Ed_cap)
-    pb = primal._collate_padded(ids, (N_cap, E_cap), spoil, check=False)
-    db = dual._collate_padded(ids, (E_cap + 2, Ed_cap), spoil, check=False)
+    if ragged:
+        B, dev = int(ids.shape[0]), ids.device
+        if B < 1:
+            raise ValueError("collate_padded_pair needs at least one graph slot")
+        node_ptr, edge_ptr, dual_edge_ptr = (torch.empty(B + 1, dtype=torch.int64, device=dev) for _ in range(3))
+        state, safe = torch.empty(2, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+        empty = torch.empty(B, dtype=torch.bool, device=dev)
+        call("gsat_ragged_pair_scan", ptr(ids), B, ptr(primal.node_ptr_all), ptr(primal.edge_ptr_all), ptr(dual.edge_ptr_all),
+             primal.num_graphs, N_cap, E_cap, Ed_cap, ptr(node_ptr), ptr(edge_ptr), ptr(dual_edge_ptr), ptr(state), ptr(safe), ptr(empty),
+             stream())
+        pb = primal._collate_padded(ids, (N_cap, E_cap), check=False, ragged=True, scan=(node_ptr, edge_ptr, state, safe, empty))
+        db = dual._collate_padded(ids, (E_cap + 2, Ed_cap), check=False, ragged=True, scan=(edge_ptr, dual_edge_ptr, state, safe, empty))
+    else:
+        n, e, ed = primal.node_counts[ids].sum(), primal.edge_counts[ids].sum(), dual.edge_counts[ids].sum()
+        spoil = (n + 2 > N_cap) | (e > E_cap) | (ed > Ed_cap)
+        pb = primal._collate_padded(ids, (N_cap, E_cap), spoil, check=False)
+        db = dual._collate_padded(ids, (E_cap + 2, Ed_cap), spoil, check=False)
     pb.pair, db.pair = db, pb
     if not sync_free() and int(pb.valid[3]):
         raise ValueError(f"collate_padded_pair: the batch does not fit the capacity (N_cap, E_cap, E_dual_cap) = ({N_cap}, {E_cap}, {Ed_cap}) "

@@ -446,6 +446,66 @@ __global__ __launch_bounds__(RSB) void k_ragged_scan(const int64_t* __restrict__
     }
 }
 
+// k_ragged_scan for a primal / dual pair: a third scan (the slots' dual edge counts) and the JOINT verdict.  spoiled is also set when
+// the totals break N + 2 <= N_cap, E <= E_cap or E_dual <= E_dual_cap, so both collations of the pair -- the dual side's node scan is
+// out_edge_ptr -- read one state and overflow together.  Every thread ends the loop with the three totals in its carries.
+__global__ __launch_bounds__(RSB) void k_ragged_pair_scan(const int64_t* __restrict__ ids, int B, const int64_t* __restrict__ node_ptr_all,
+                                                          const int64_t* __restrict__ edge_ptr_all,
+                                                          const int64_t* __restrict__ dual_edge_ptr_all, int64_t G_all, int64_t N_cap,
+                                                          int64_t E_cap, int64_t Ed_cap, int64_t* __restrict__ out_node_ptr,
+                                                          int64_t* __restrict__ out_edge_ptr, int64_t* __restrict__ out_dual_edge_ptr,
+                                                          int64_t* __restrict__ state, int64_t* __restrict__ safe_ids,
+                                                          uint8_t* __restrict__ empty) {
+    __shared__ int64_t sn[RSB], se[RSB], sd[RSB];
+    __shared__ int s_filled, s_first_empty, s_last_filled, s_bad;
+    const int t = threadIdx.x;
+    if (t == 0) { s_filled = 0; s_first_empty = 0x7fffffff; s_last_filled = -1; s_bad = 0; }
+    int64_t carry_n = 0, carry_e = 0, carry_d = 0;
+    int filled = 0, first_empty = 0x7fffffff, last_filled = -1, bad = 0;
+    for (int base = 0; base < B; base += RSB) {
+        const int i = base + t;
+        int64_t n = 0, e = 0, d = 0;
+        if (i < B) {
+            const int64_t id = ids[i];
+            const bool ok = id >= 0 && id < G_all;
+            if (ok) {
+                n = node_ptr_all[id + 1] - node_ptr_all[id];
+                e = edge_ptr_all[id + 1] - edge_ptr_all[id];
+                d = dual_edge_ptr_all[id + 1] - dual_edge_ptr_all[id];
+            }
+            if (id >= 0) { ++filled; last_filled = i; } else { first_empty = min(first_empty, i); }
+            if (id >= G_all) bad = 1;
+            safe_ids[i] = ok ? id : 0;
+            empty[i] = id < 0 ? 1 : 0;
+        }
+        __syncthreads();                                    // the previous chunk's totals have been read
+        sn[t] = n; se[t] = e; sd[t] = d;
+        __syncthreads();
+        for (int o = 1; o < RSB; o <<= 1) {
+            const int64_t a = t >= o ? sn[t - o] : 0, b = t >= o ? se[t - o] : 0, c = t >= o ? sd[t - o] : 0;
+            __syncthreads();
+            sn[t] += a; se[t] += b; sd[t] += c;
+            __syncthreads();
+        }
+        if (i < B) {
+            out_node_ptr[i + 1] = carry_n + sn[t]; out_edge_ptr[i + 1] = carry_e + se[t]; out_dual_edge_ptr[i + 1] = carry_d + sd[t];
+        }
+        carry_n += sn[RSB - 1]; carry_e += se[RSB - 1]; carry_d += sd[RSB - 1];
+    }
+    __syncthreads();
+    atomicAdd(&s_filled, filled);                           // integer LDS atomics: any order gives the same result
+    atomicMin(&s_first_empty, first_empty);
+    atomicMax(&s_last_filled, last_filled);
+    atomicOr(&s_bad, bad);
+    __syncthreads();
+    if (t == 0) {
+        out_node_ptr[0] = 0; out_edge_ptr[0] = 0; out_dual_edge_ptr[0] = 0;
+        const bool fits = carry_n + 2 <= N_cap && carry_e <= E_cap && carry_d <= Ed_cap;
+        state[0] = s_filled;
+        state[1] = (s_bad || s_last_filled > s_first_empty || !fits) ? 1 : 0;
+    }
+}
+
 }  // namespace gsat
 
 extern "C" {
@@ -459,6 +519,23 @@ int gsat_ragged_scan(const int64_t* graph_ids, int64_t num_slots, const int64_t*
                  "gsat_ragged_scan: null pointer");
     gsat::k_ragged_scan<<<1, gsat::RSB, 0, stream>>>(graph_ids, (int)num_slots, node_ptr_all, edge_ptr_all, num_graphs_all, out_node_ptr,
                                                      out_edge_ptr, state, safe_ids, empty);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_ragged_pair_scan(const int64_t* graph_ids, int64_t num_slots, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
+                          const int64_t* dual_edge_ptr_all, int64_t num_graphs_all, int64_t N_cap, int64_t E_cap, int64_t E_dual_cap,
+                          int64_t* out_node_ptr, int64_t* out_edge_ptr, int64_t* out_dual_edge_ptr, int64_t* state, int64_t* safe_ids,
+                          uint8_t* empty, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(num_slots >= 1 && num_slots < (1ll << 31) - 1 && num_graphs_all >= 0, GSAT_ERR_ARG, "gsat_ragged_pair_scan: bad extents");
+    GSAT_REQUIRE(N_cap >= 2 && N_cap < (1ll << 31) && E_cap >= 0 && E_cap < (1ll << 31) - 2 && E_dual_cap >= 0 && E_dual_cap < (1ll << 31),
+                 GSAT_ERR_ARG, "gsat_ragged_pair_scan: bad capacity (two padding nodes; the dual node capacity E_cap + 2 stays below 2^31)");
+    GSAT_REQUIRE(graph_ids && node_ptr_all && edge_ptr_all && dual_edge_ptr_all && out_node_ptr && out_edge_ptr && out_dual_edge_ptr &&
+                 state && safe_ids && empty, GSAT_ERR_ARG, "gsat_ragged_pair_scan: null pointer");
+    gsat::k_ragged_pair_scan<<<1, gsat::RSB, 0, stream>>>(graph_ids, (int)num_slots, node_ptr_all, edge_ptr_all, dual_edge_ptr_all,
+                                                          num_graphs_all, N_cap, E_cap, E_dual_cap, out_node_ptr, out_edge_ptr,
+                                                          out_dual_edge_ptr, state, safe_ids, empty);
     GSAT_LAUNCH_CHECK();
     return GSAT_OK;
 }

@@ -145,8 +145,9 @@ class DualGSAT(nn.Module):
         """``dual_forward_pass`` on a padded pair (collate_padded_pair): dual node row k < Ep is primal edge slot k.  Every primal module runs
         inside ``padded(pb.valid)``, every dual one inside ``padded(db.valid)``; the whole-batch reductions take their counts from the
         device (f1 and the primal info loss: pb.valid[1]; the dual info loss: db.valid[1], with ``db.r`` -- one device float, when set --
-        as its r); both criteria see the real graphs ``[:B]``.  No host decision depends on the batch, so the call can be captured; every
-        output has capacity shape."""
+        as its r); both criteria see the real graphs ``[:B]`` -- of a ragged pair (``collate_padded_pair(..., ragged=True)``) the ``B`` graph
+        slots, of which they read the filled count ``pb.valid[2]`` on the device (``criterion_valid``).  No host decision depends on the
+        batch, so the call can be captured; every output has capacity shape."""
         from .graph_index import get_index
         if self.primal_learn_edge_att or self.dual_learn_edge_att:
             raise ValueError("a padded pair takes node attention on both sides (the MUTAG configs), not edge attention")
@@ -158,6 +159,10 @@ class DualGSAT(nn.Module):
         B = int(pb.num_graphs) - 1
         if Nd != Ep + 2 or int(db.num_graphs) - 1 != B:
             raise ValueError("not a padded pair: the dual node capacity must be the primal edge capacity + 2, with the same graphs")
+        ragged = bool(getattr(pb, "ragged", False))
+        if ragged != bool(getattr(db, "ragged", False)):
+            raise ValueError("not a padded pair: one side is ragged and the other is not (collate_padded_pair(..., ragged=True) makes both)")
+        g_valid = pb.valid[2:3] if ragged else None          # filled slots (= db.valid[2:3]), read by the criterion kernel
         pctx, dctx = (lambda: padded(pb.valid, pb.capacity)), (lambda: padded(db.valid, db.capacity))
         for d in (pb, db):
             get_index(d.edge_index, d.x.shape[0]).graphs(d.batch, int(d.num_graphs))
@@ -188,8 +193,8 @@ class DualGSAT(nn.Module):
         with dctx():
             dual_clf_logits = self.dual_clf(db.x, db.edge_index, db.batch, edge_attr=db.edge_attr, edge_atten=dual_edge_att)
         # __loss__ with counts: the same terms, coefficients, order of the sum and loss dict -- change the two together
-        primal_pred_loss = self.primal_criterion(primal_clf_logits[:B], pb.y[:B]) * self.primal_pred_loss_coef
-        dual_pred_loss = self.dual_criterion(dual_clf_logits[:B], db.y[:B]) * self.dual_pred_loss_coef
+        primal_pred_loss = self.primal_criterion(primal_clf_logits[:B], pb.y[:B], g_valid=g_valid) * self.primal_pred_loss_coef
+        dual_pred_loss = self.dual_criterion(dual_clf_logits[:B], db.y[:B], g_valid=g_valid) * self.dual_pred_loss_coef
         dual_r = self.dual_fix_r if self.dual_fix_r else get_r(self.dual_decay_interval, self.dual_decay_r, epoch,
                                                                 final_r=self.dual_final_r, init_r=self.dual_init_r)
         dual_info_loss = InfoLoss.apply(edge_tensor(dual_edge_att), dual_r, db.valid[1:2], getattr(db, "r", None)) * self.dual_info_loss_coef

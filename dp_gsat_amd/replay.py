@@ -96,7 +96,7 @@ def _mix_epoch(m, mixed):
     return m.mix_after_epoch + (1 if mixed else 0)
 
 
-def _padded_pair_setup(obj, m, primal_ds, dual_ds, batch_size, capacity, graphs):
+def _padded_pair_setup(obj, m, primal_ds, dual_ds, batch_size, capacity, graphs, ragged=False):
     """The refusals of a replayed padded pair (those ``DualGSAT._pair_forward_pass`` makes, before anything is captured), then the
     static inputs of the pair on ``obj``."""
     if m.primal_criterion.multi_label or m.dual_criterion.multi_label:
@@ -105,12 +105,13 @@ def _padded_pair_setup(obj, m, primal_ds, dual_ds, batch_size, capacity, graphs)
         raise ValueError("a padded pair takes node attention on both sides (the MUTAG configs), not edge attention")
     primal_ds.check_pair(dual_ds)
     obj.model, obj.primal_ds, obj.dual_ds = m, primal_ds, dual_ds
-    obj._setup(m, (primal_ds, dual_ds), batch_size, capacity, graphs)
+    obj._setup(m, (primal_ds, dual_ds), batch_size, capacity, graphs, ragged)
 
 
-def _first_budget_row(dataset, capacity, batch_size):
-    """The ids a ragged instance warms up and captures on: the first batch budget batching cuts from the dataset in storage order."""
-    return dataset.budget_batches(torch.arange(dataset.num_graphs), capacity, batch_size)[0].contiguous()
+def _first_budget_row(dataset, capacity, batch_size, dual=None):
+    """The ids a ragged instance warms up and captures on: the first batch budget batching cuts from the dataset in storage order (of a
+    pair: under its three budgets)."""
+    return dataset.budget_batches(torch.arange(dataset.num_graphs), capacity, batch_size, dual=dual)[0].contiguous()
 
 
 class _Replayed:
@@ -134,7 +135,7 @@ class _Replayed:
         dev = ds.x_all.device
         self.ragged = bool(ragged)
         if self.ragged:
-            self.graph_ids = _first_budget_row(ds, self.capacity, self.batch_size)
+            self.graph_ids = _first_budget_row(ds, self.capacity, self.batch_size, datasets[1] if self._pair else None)
         else:
             self.graph_ids = torch.arange(self.batch_size, dtype=torch.int64, device=dev)
         self.r = torch.full((1,), float(self._r_of(0)), dtype=torch.float32, device=dev)
@@ -220,8 +221,9 @@ class _Replayed:
         return self._outputs[mixed].get("loss")
 
     def batches(self, perm) -> torch.Tensor:
-        """``dataset.budget_batches(perm, self.capacity, self.batch_size)``: the rows to feed ``step`` of a ragged instance."""
-        return self._datasets[0].budget_batches(perm, self.capacity, self.batch_size)
+        """``dataset.budget_batches(perm, self.capacity, self.batch_size)``: the rows to feed ``step`` of a ragged instance -- of a pair
+        the three-budget rows, ``primal_ds.budget_batches(perm, self.capacity, self.batch_size, dual=dual_ds)``."""
+        return self._datasets[0].budget_batches(perm, self.capacity, self.batch_size, dual=self._datasets[1] if self._pair else None)
 
     def check_epoch(self, perm) -> None:
         """Raise ValueError if a full batch of the epoch ``perm`` (graph ids in visiting order) exceeds the capacity -- in nodes, edges
@@ -333,14 +335,20 @@ class ReplayedDualStep(_Replayed):
     After a step: ``loss`` (device scalar), ``clf_logits`` [B + 1, C] (primal), ``batch`` / ``dual_batch`` (the padded pair) and, with
     ``keep_edge_att=True``, ``edge_att`` [E_cap, 1]; all overwritten by the next replay of the same graph.  ``p.grad`` of every
     parameter points at the gradients of the graph that ran last.  ``graphs``: an own pair of ``torch.cuda.CUDAGraph`` (unmixed, mixed) to
-    capture into (with debug mode on, to dump them)."""
+    capture into (with debug mode on, to dump them).
+
+    ``ragged=True``: as in ``ReplayedStep`` -- ``batch_size`` graph slots; both graphs hold ``collate_padded_pair(..., ragged=True)`` and
+    both criteria read the number of filled slots on the device, so ``step`` takes 1 to ``batch_size`` ids (or a row of ``batches``) and no
+    tail batch is left to run eagerly.  ``batches(perm)`` packs an epoch under the three budgets (nodes, edges, dual edges), which lets
+    the capacity be sized near the mean batch.  Warm-up and capture run on the first such batch of the dataset in storage order.  An
+    overflow pair has no filled slot: both criteria give 0, the f1 term its constant 1."""
 
     def __init__(self, dual_gsat, primal_ds, dual_ds, batch_size: int, capacity: Optional[tuple] = None, pinned: bool = False,
-                 keep_edge_att: bool = False, graphs=None):
+                 keep_edge_att: bool = False, graphs=None, ragged: bool = False):
         m = dual_gsat
         for side, opt in (("primal", m.primal_optimizer), ("dual", m.dual_optimizer)):
             _need_capturable(opt, f"ReplayedDualStep needs a capturable {side} optimizer")
-        _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs)
+        _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs, ragged)
         dev = primal_ds.x_all.device
         self.keep_edge_att, self.pinned = bool(keep_edge_att), bool(pinned)
         self.primal_noise = self.dual_noise = self.primal_masks = self.dual_masks = None
@@ -364,7 +372,7 @@ class ReplayedDualStep(_Replayed):
         """The step body (what one graph holds), run on the current stream."""
         m = self.model
         clear_cache()
-        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
+        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity, ragged=self.ragged)
         db.r = self.r
         self._overflow.bitwise_or_(pb.valid[3:4])
         att, loss, _, logits = m.dual_forward_pass(pb, db, _mix_epoch(m, mixed), True, self.primal_noise, self.dual_noise,
@@ -538,18 +546,22 @@ class ReplayedDualEval(_Replayed):
     Refused with ValueError before anything is captured: what a padded pair refuses (the multi-label criterion, edge attention,
     ``check_pair``, a capacity that is no triple), ``sync_group`` BatchNorm, a model without ``dual_forward_pass`` and a dataset without
     edge labels or graph labels.  Overflow of the joint capacity sets the log's flag bit 0 and is raised by ``run``; ``check_epoch``
-    tells beforehand."""
+    tells beforehand.
+
+    ``ragged=True``: as in ``ReplayedEval`` -- ``batch_size`` graph slots, ``step`` takes 1 to ``batch_size`` ids, and ``run`` packs its ids
+    under the three budgets (``batches``) and replays EVERY batch: no eager tail, no ``collate``.  The logs then have room for one batch
+    per graph.  The seed stream advances by one word per batch as before, so batch j of a run is the j-th row of ``batches``."""
 
     def __init__(self, dual_gsat, primal_ds, dual_ds, batch_size: int, k: int, capacity: Optional[tuple] = None, bins: int = 64,
                  max_graphs: Optional[int] = None, max_edges: Optional[int] = None, score_dual: bool = False, seed: Optional[int] = None,
-                 graphs=None):
+                 graphs=None, ragged: bool = False):
         m = dual_gsat
         if not hasattr(m, "dual_forward_pass"):
             raise ValueError("ReplayedDualEval replays DualGSAT.dual_forward_pass; ReplayedEval covers a plain GSAT")
         _refuse_sync_group(m)
         if primal_ds.edge_label_all is None or primal_ds.y_all is None or dual_ds.y_all is None:
             raise ValueError("ReplayedDualEval needs datasets with edge labels (primal) and graph labels")
-        _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs)
+        _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs, ragged)
         if seed is None:        # a fixed mix of torch.initial_seed(): follows torch.manual_seed, draws nothing
             seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & 0x7FFFFFFFFFFFFFFF
         self.base = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -570,7 +582,7 @@ class ReplayedDualEval(_Replayed):
         self.seed_state.copy_(torch.tensor([signed(self.base), signed(int(counter) & 0xFFFFFFFFFFFFFFFF)], dtype=torch.int64))
 
     def _make_logs(self, sizes):
-        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
+        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity, ragged=self.ragged)
         with torch.no_grad():
             logits = self.model.dual_forward_pass(pb, db, 0, False, dual_seed=0)[3]
         logs = _new_logs(self, 2 if self.score_dual else 1, logits, *sizes)
@@ -603,7 +615,7 @@ class ReplayedDualEval(_Replayed):
     def run_once(self, mixed: bool):
         """The body of one captured graph, run on the current stream."""
         clear_cache()
-        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity)
+        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity, ragged=self.ragged)
         db.r = self.r
         att, logits, losses, dual_att, word = self._forward(pb, db, _mix_epoch(self.model, mixed))
         self._publish(mixed, batch=pb, dual_batch=db, edge_att=att, clf_logits=logits, losses=losses, dual_att=dual_att, _word=word)
@@ -613,7 +625,7 @@ class ReplayedDualEval(_Replayed):
         32) and the logs are reset; every full batch is a replay, the tail of fewer than ``batch_size`` graphs runs eagerly (both
         datasets' ``collate``, the same eval-mode forward with the next seed word, the same appends), and ``log.compute()`` gives the
         scores -- with ``score_dual`` also ``dual_att_auroc``, ``dual_precision@k``, ``dual_delta_kl``, ``dual_avg_signal_att_weights`` and
-        ``dual_avg_bkg_att_weights`` of the dual attention."""
+        ``dual_avg_bkg_att_weights`` of the dual attention.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
         self._set_seed_state(int(epoch) << 32)
         res = _run_epoch(self, graph_ids, epoch)
         if self.dual_log is not None:

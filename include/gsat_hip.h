@@ -691,6 +691,19 @@ int gsat_ragged_scan(const int64_t* graph_ids, int64_t num_slots, const int64_t*
                      uint8_t* empty, void* stream);
 
 /*
+ * gsat_ragged_scan for a primal / dual pair (a dataset and its line-graph dataset), one launch of one block: a third exclusive scan,
+ * out_dual_edge_ptr int64[num_slots + 1], of the slots' dual edge counts (dual_edge_ptr_all: the dual dataset's edge_ptr_all), and
+ * the JOINT verdict.  spoiled = 1 when a filled slot follows an empty one, an id is not below num_graphs_all, or the totals break
+ * N + 2 <= N_cap, E <= E_cap or E_dual <= E_dual_cap (totals in int64; every capacity below 2^31, E_cap below 2^31 - 2 because the
+ * dual node capacity is E_cap + 2).  The dual side's node scan is out_edge_ptr; both sides share safe_ids, empty and state, so that
+ * gsat_collate_padded_ragged(..., state, ...) on either side overflows exactly when the other does.  Integer sums; capturable.
+ */
+int gsat_ragged_pair_scan(const int64_t* graph_ids, int64_t num_slots, const int64_t* node_ptr_all, const int64_t* edge_ptr_all,
+                          const int64_t* dual_edge_ptr_all, int64_t num_graphs_all, int64_t N_cap, int64_t E_cap, int64_t E_dual_cap,
+                          int64_t* out_node_ptr, int64_t* out_edge_ptr, int64_t* out_dual_edge_ptr, int64_t* state, int64_t* safe_ids,
+                          uint8_t* empty, void* stream);
+
+/*
  * gsat_collate_padded with a graph count read on the device: ragged_state int64[2] = (filled slots, spoiled) and the scans are
  * gsat_ragged_scan's, so the empty slots own no node and no edge and their graph_ids entries are never dereferenced.  valid[2] = the
  * number of filled slots; a spoiled batch is an overflow like one that does not fit, and an overflow batch has valid == (0, 0, 0, 1).
