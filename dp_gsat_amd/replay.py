@@ -17,6 +17,7 @@ import torch
 from ._lib import call, ptr, stream
 from .collate import collate_padded_pair
 from .eval_log import EpochLog
+from .evaluate import MAX_BINS
 from .graph_index import clear_cache, set_sync_free, sync_free
 from .gsat import get_r
 from .ops import edge_tensor
@@ -247,8 +248,11 @@ class _Replayed:
 def _capture_training(rs, optimizers):
     """Make the overflow flag of a training class and capture its graphs; nothing has trained afterwards."""
     rs._overflow = torch.zeros(1, dtype=torch.int32, device=rs.r.device)
-    with _kept_training_state(rs._model, optimizers), _capture_mode(rs._model):
-        rs._warm_up_and_capture()
+    try:
+        with _kept_training_state(rs._model, optimizers), _capture_mode(rs._model):
+            rs._warm_up_and_capture(None, lambda: _reset_logs(rs))      # the warm-up runs appended: the logs are empty afterwards
+    finally:
+        _reset_logs(rs)
     rs._overflow.zero_()
 
 
@@ -258,7 +262,53 @@ def _take_overflow(rs):
     return seen
 
 
-class ReplayedStep(_Replayed):
+def _training_log_setup(rs, log_k, bins, max_graphs, max_edges):
+    """``log_k`` None: no log.  Else the sizes of the training-pass log(s) on ``rs``, refused here -- before anything is captured -- where
+    ``EpochLog`` or its ``append`` would refuse them.  The logs themselves are made by the first warm-up run, which knows the logits."""
+    rs.log = rs.dual_log = None
+    rs._log_sizes = None
+    if log_k is None:
+        return
+    ds = rs._datasets[0]
+    if ds.edge_label_all is None or ds.y_all is None:
+        raise ValueError(f"{type(rs).__name__}(log_k=) needs a dataset with edge labels and graph labels")
+    rs._log_sizes = (int(log_k), int(bins), max_graphs, max_edges)
+
+
+def _append_training(rs, att, dual_att, b, logits, loss_dict):
+    """The end of a logging step body: append this step's training-mode attention on the edges, its logits and its (loss, pred, info) to
+    ``rs.log`` -- and, where ``dual_att`` is given, the same with the dual attention to ``rs.dual_log``.  Kernels that read the step's
+    outputs and write the logs' own arrays: nothing is drawn and nothing that trains is written.  Returns the [3] loss tensor."""
+    with torch.no_grad():
+        att, logits = edge_tensor(att).detach(), logits.detach()
+        if rs.log is None:          # the first warm-up run
+            logs = _new_logs(rs, 1 if dual_att is None else 2, logits, *rs._log_sizes)
+            rs.log, rs.dual_log = logs[0], logs[1] if dual_att is not None else None
+        losses = _loss_triple(loss_dict)
+        rs.log.append(att, b, logits, losses)
+        if dual_att is not None:
+            rs.dual_log.append(dual_att, b, logits, losses)
+    return losses
+
+
+class _TrainingLog:
+    """``begin_epoch`` / ``epoch_scores`` of the two training classes (constructed with ``log_k``)."""
+
+    def begin_epoch(self) -> None:
+        """Empty the training-pass log(s) on the device; nothing is read.  Without ``log_k`` there is nothing to empty."""
+        _reset_logs(self)
+
+    def epoch_scores(self) -> dict:
+        """``log.compute()`` -- two host reads -- over the steps since ``begin_epoch()``: the keys ``ReplayedEval.run`` returns (with
+        ``score_dual`` also the ``dual_`` keys of ``ReplayedDualEval.run``), scored on the training-mode (sampled) attention and logits each
+        step produced; ``loss``, ``pred`` and ``info`` are the means over the steps.  ValueError without ``log_k``, before any step, and
+        when a step since ``begin_epoch()`` did not fit the capacity (it appended nothing; ``overflowed()`` still reports it)."""
+        if self.log is None:
+            raise ValueError(f"{type(self).__name__} was constructed without log_k: it keeps no log of the training pass")
+        return _scores(self)
+
+
+class ReplayedStep(_Replayed, _TrainingLog):
     """``ReplayedStep(gsat, dataset, batch_size, capacity=None)``: captures clear_cache, collate_padded, forward_pass,
     zero_grad(set_to_none=True), backward and optimizer.step() of ``gsat`` on ``dataset`` (a PackedDataset) once, after three warm-up
     runs on a side stream.  ``gsat.optimizer`` must be capturable (``torch.optim.Adam(..., capturable=True)``).  The warm-up runs
@@ -283,17 +333,39 @@ class ReplayedStep(_Replayed):
     capacity be sized near the mean batch instead of the worst one.  Warm-up and capture run on the first such batch of the dataset in
     storage order, so a capacity that graphs 0 .. batch_size-1 exceed is fine.  An overflow batch has no filled slot: its loss is exactly
     0 and neither loss term produces a gradient (the optimizer still steps on the weight decay, and BatchNorm still sees an empty
-    batch)."""
+    batch).
+
+    ``log_k=k`` (with ``bins``, ``max_graphs``, ``max_edges`` as in ``ReplayedEval``): the training pass logs itself.  ``log`` is an
+    :class:`~dp_gsat_amd.eval_log.EpochLog` (the dataset needs edge labels and graph labels) and the captured body ends in
+    ``log.append`` of the step's training-mode (sampled) attention on the edges, the padded batch, the logits and the (loss, pred, info)
+    of its loss dict -- two more launches per replay, also kept in ``losses`` [3].  ``begin_epoch()`` empties the log and
+    ``epoch_scores()`` scores the steps since: what the reference's ``run_one_epoch(..., 'train')`` returns, without a second pass over
+    the training ids and without eager work per step::
+
+        rs.begin_epoch()
+        for row in rs.batches(perm):                  # ragged: every batch is a replay
+            rs.step(row, epoch)
+        train_res = rs.epoch_scores()                 # att_auroc, precision@k, clf_acc, clf_roc, loss, pred, info, ...
+
+    A fixed-count instance leaves the tail batch to the caller, and so its append: after the eager step on ``b = dataset.collate(tail)``,
+    ``rs.log.append(att, b, logits, torch.stack([ld["loss"], ld["pred"], ld["info"]]))`` (with ``gsat.sync_loss_dict = False``, or
+    ``torch.tensor([...], device=...)`` of the floats).  Warm-up and capture leave the log empty.  Logging reads the step's outputs and
+    writes only the log: it draws nothing from the device seed stream or torch's generators and touches no parameter, buffer or
+    optimizer state, so a run with ``log_k`` trains bit for bit like one without.  A step that did not fit the capacity appends nothing
+    and makes ``epoch_scores()`` raise.  Without ``log_k`` the captured graph is the one described above, launch for launch."""
 
     def __init__(self, gsat, dataset, batch_size: int, capacity: Optional[tuple] = None, keep_edge_att: bool = False, graph=None,
-                 ragged: bool = False):
+                 ragged: bool = False, log_k: Optional[int] = None, bins: int = 64, max_graphs: Optional[int] = None,
+                 max_edges: Optional[int] = None):
+        _check_log_sizes(log_k, bins)
         _need_capturable(gsat.optimizer, "ReplayedStep needs a capturable optimizer")
         if getattr(gsat.criterion, "multi_label", False):
             raise ValueError(_MULTI_LABEL)
         self.gsat, self.dataset = gsat, dataset
         self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
+        _training_log_setup(self, log_k, bins, max_graphs, max_edges)
         self.keep_edge_att = bool(keep_edge_att)
-        self.batch = self.loss = self.clf_logits = self.edge_att = None
+        self.batch = self.loss = self.clf_logits = self.edge_att = self.losses = None
         _capture_training(self, (gsat.optimizer,))
 
     def run_once(self):
@@ -303,12 +375,13 @@ class ReplayedStep(_Replayed):
         b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
         b.r = self.r
         self._overflow.bitwise_or_(b.valid[3:4])
-        att, loss, _, logits = gsat.forward_pass(b, 0, True)
+        att, loss, loss_dict, logits = gsat.forward_pass(b, 0, True)
         gsat.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         gsat.optimizer.step()
+        extra = {} if self._log_sizes is None else {"losses": _append_training(self, att, None, b, logits, loss_dict)}
         self._publish(False, batch=b, loss=loss.detach(), clf_logits=logits.detach(),
-                      edge_att=edge_tensor(att).detach() if self.keep_edge_att else None)
+                      edge_att=edge_tensor(att).detach() if self.keep_edge_att else None, **extra)
 
     def overflowed(self) -> bool:
         """True if a step since the last call (or since capture) got a batch that did not fit the capacity.  One host read; clears
@@ -316,7 +389,7 @@ class ReplayedStep(_Replayed):
         return _take_overflow(self)
 
 
-class ReplayedDualStep(_Replayed):
+class ReplayedDualStep(_Replayed, _TrainingLog):
     """``ReplayedDualStep(dual_gsat, primal_ds, dual_ds, batch_size, capacity=None)``: the dual/primal training step (DualGSAT) over a
     dataset and its dual (``primal_ds.line_graph_dataset()``) as replays of captured hipGraphs.  One replay holds clear_cache,
     collate_padded_pair, dual_forward_pass, both zero_grad(set_to_none=True), the backward and both optimizer steps.  Both optimizers
@@ -341,14 +414,26 @@ class ReplayedDualStep(_Replayed):
     both criteria read the number of filled slots on the device, so ``step`` takes 1 to ``batch_size`` ids (or a row of ``batches``) and no
     tail batch is left to run eagerly.  ``batches(perm)`` packs an epoch under the three budgets (nodes, edges, dual edges), which lets
     the capacity be sized near the mean batch.  Warm-up and capture run on the first such batch of the dataset in storage order.  An
-    overflow pair has no filled slot: both criteria give 0, the f1 term its constant 1."""
+    overflow pair has no filled slot: both criteria give 0, the f1 term its constant 1.
+
+    ``log_k=k``: as in ``ReplayedStep`` -- both graphs end in ``log.append`` of what ``dual_train_one_batch`` returns and
+    ``ReplayedDualEval`` logs: the primal attention on the edges (mixed, in the mixed graph), the primal logits and the loss dict, whose
+    ``pred`` and ``info`` are the dual model's.  ``score_dual=True`` keeps a second log, ``dual_log``, of the dual attention on the primal
+    edge slots (``dual_att`` [E_cap, 1] after a step), and ``epoch_scores()`` adds its attention scores under the ``dual_`` prefix of
+    ``ReplayedDualEval.run``.  ``begin_epoch()`` empties both logs."""
 
     def __init__(self, dual_gsat, primal_ds, dual_ds, batch_size: int, capacity: Optional[tuple] = None, pinned: bool = False,
-                 keep_edge_att: bool = False, graphs=None, ragged: bool = False):
+                 keep_edge_att: bool = False, graphs=None, ragged: bool = False, log_k: Optional[int] = None, score_dual: bool = False,
+                 bins: int = 64, max_graphs: Optional[int] = None, max_edges: Optional[int] = None):
         m = dual_gsat
+        _check_log_sizes(log_k, bins)
+        if score_dual and log_k is None:
+            raise ValueError("score_dual scores a second training-pass log: it needs log_k")
         for side, opt in (("primal", m.primal_optimizer), ("dual", m.dual_optimizer)):
             _need_capturable(opt, f"ReplayedDualStep needs a capturable {side} optimizer")
         _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs, ragged)
+        _training_log_setup(self, log_k, bins, max_graphs, max_edges)
+        self.score_dual = bool(score_dual)
         dev = primal_ds.x_all.device
         self.keep_edge_att, self.pinned = bool(keep_edge_att), bool(pinned)
         self.primal_noise = self.dual_noise = self.primal_masks = self.dual_masks = None
@@ -358,7 +443,7 @@ class ReplayedDualStep(_Replayed):
             self.dual_noise = torch.rand(E_cap + 2, 1, device=dev)
             self.primal_masks = self._keep_masks(m.primal_extractor, N_cap, dev)
             self.dual_masks = self._keep_masks(m.dual_extractor, E_cap + 2, dev)
-        self.batch = self.dual_batch = self.loss = self.clf_logits = self.edge_att = None
+        self.batch = self.dual_batch = self.loss = self.clf_logits = self.edge_att = self.losses = self.dual_att = None
         self._grads = {}
         _capture_training(self, (m.primal_optimizer, m.dual_optimizer))
 
@@ -375,8 +460,15 @@ class ReplayedDualStep(_Replayed):
         pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity, ragged=self.ragged)
         db.r = self.r
         self._overflow.bitwise_or_(pb.valid[3:4])
-        att, loss, _, logits = m.dual_forward_pass(pb, db, _mix_epoch(m, mixed), True, self.primal_noise, self.dual_noise,
-                                                   self.primal_masks, self.dual_masks)
+        kept = m.keep_dual_att
+        m.keep_dual_att = kept or self.score_dual
+        try:
+            att, loss, loss_dict, logits = m.dual_forward_pass(pb, db, _mix_epoch(m, mixed), True, self.primal_noise, self.dual_noise,
+                                                               self.primal_masks, self.dual_masks)
+            dual_att = m.dual_att[:self.capacity[1]] if self.score_dual else None
+        finally:
+            if self.score_dual:
+                m.keep_dual_att, m.dual_att = kept, None
         m.primal_optimizer.zero_grad(set_to_none=True)
         m.dual_optimizer.zero_grad(set_to_none=True)
         loss.backward()
@@ -384,8 +476,10 @@ class ReplayedDualStep(_Replayed):
         m.dual_optimizer.step()
         self._grads[mixed] = [(p, p.grad) for opt in (m.primal_optimizer, m.dual_optimizer) for grp in opt.param_groups
                               for p in grp["params"]]
+        extra = {} if self._log_sizes is None else {"losses": _append_training(self, att, dual_att, pb, logits, loss_dict),
+                                                    "dual_att": dual_att}
         self._publish(mixed, batch=pb, dual_batch=db, loss=loss.detach(), clf_logits=logits.detach(),
-                      edge_att=edge_tensor(att).detach() if self.keep_edge_att else None)
+                      edge_att=edge_tensor(att).detach() if self.keep_edge_att else None, **extra)
 
     def _select(self, mixed):
         for p, g in self._grads[mixed]:          # each graph wrote the gradients into tensors of its own
@@ -410,14 +504,38 @@ def _new_logs(ev, count, logits, k, bins, max_graphs, max_edges):
     return [EpochLog(k, mg, me, max(most, 1), int(logits.shape[1]), y_cols, bins, False, ds.x_all.device) for _ in range(count)]
 
 
+def _check_log_sizes(k, bins):
+    """What ``EpochLog`` refuses of ``log_k`` (None: no log) and ``bins``, said before anything is captured."""
+    if k is None:
+        return
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("log_k must be a positive int (the k of precision@k), or None for no log")
+    if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= MAX_BINS:
+        raise ValueError(f"need 1 <= bins <= {MAX_BINS}")
+
+
 def _loss_triple(loss_dict):
     return torch.stack([loss_dict[key].reshape(()) for key in ("loss", "pred", "info")]).to(torch.float32)
+
+
+_DUAL_SCORES = ("att_auroc", "precision@{k}", "delta_kl", "avg_signal_att_weights", "avg_bkg_att_weights")
 
 
 def _reset_logs(ev):
     for log in (ev.log, getattr(ev, "dual_log", None)):
         if log is not None:
             log.reset()
+
+
+def _scores(ev):
+    """``log.compute()`` and, from a second log of the dual attention, its attention scores under a ``dual_`` prefix."""
+    res = ev.log.compute()
+    if getattr(ev, "dual_log", None) is not None:
+        dual = ev.dual_log.compute()
+        for key in _DUAL_SCORES:
+            key = key.format(k=ev.log.k)
+            res["dual_" + key] = dual[key]
+    return res
 
 
 def _capture_evaluator(ev, make_logs):
@@ -442,7 +560,7 @@ def _run_epoch(ev, graph_ids, epoch):
         with _forward_mode(ev._model, True):
             tail = ids[n - left:].to(ev.graph_ids.device, torch.int64)
             ev._forward(*[ds.collate(tail) for ds in ev._datasets], epoch)
-    return ev.log.compute()
+    return _scores(ev)
 
 
 class ReplayedEval(_Replayed):
@@ -516,7 +634,6 @@ class ReplayedEval(_Replayed):
 # The (base, counter) states of every ReplayedDualEval: a captured graph holds its state's address in a gsat_seed_next node, so a state
 # is written in place and lives as long as the process.
 _EVAL_SEED_STATES = []
-_DUAL_SCORES = ("att_auroc", "precision@{k}", "delta_kl", "avg_signal_att_weights", "avg_bkg_att_weights")
 
 
 class ReplayedDualEval(_Replayed):
@@ -627,10 +744,4 @@ class ReplayedDualEval(_Replayed):
         scores -- with ``score_dual`` also ``dual_att_auroc``, ``dual_precision@k``, ``dual_delta_kl``, ``dual_avg_signal_att_weights`` and
         ``dual_avg_bkg_att_weights`` of the dual attention.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
         self._set_seed_state(int(epoch) << 32)
-        res = _run_epoch(self, graph_ids, epoch)
-        if self.dual_log is not None:
-            dual = self.dual_log.compute()
-            for key in _DUAL_SCORES:
-                key = key.format(k=self.log.k)
-                res["dual_" + key] = dual[key]
-        return res
+        return _run_epoch(self, graph_ids, epoch)

@@ -19,9 +19,14 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
     into batches that fill a node / edge budget (PackedDataset.budget_batches, at most ``--batch-size`` graphs each) and the capacity
     is sized from the data (the mean graph times the batch size) instead of from the worst batch.
 
+  * ``--graph --ragged --train-scores`` -- the training pass logs itself (``ReplayedStep(..., log_k=5)``): every replay appends its
+    training-mode attention, logits and losses to a device log inside the captured graph, and each report line is followed by the
+    scores of the training epoch (``epoch_scores()``: two host reads, no second pass over the training ids).
+
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --train-scores
 """
 import argparse
 import os
@@ -74,6 +79,7 @@ def main():
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, one GPU per rank) or gloo (to rehearse N ranks on one GPU)")
     ap.add_argument("--graph", action="store_true", help="train full batches as replays of one captured hipGraph (single process)")
     ap.add_argument("--ragged", action="store_true", help="with --graph: budget batches of a ragged graph count, every batch a replay")
+    ap.add_argument("--train-scores", action="store_true", help="with --graph --ragged: log the training pass and print its scores")
     args = ap.parse_args()
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -81,6 +87,8 @@ def main():
         ap.error("--graph is single-process: it replays one captured step and cannot shard a batch over ranks")
     if args.ragged and not args.graph:
         ap.error("--ragged batches are replays: it needs --graph")
+    if args.train_scores and not args.ragged:
+        ap.error("--train-scores logs replays of every batch: it needs --graph --ragged")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     if world > 1:
@@ -127,7 +135,7 @@ def main():
         n_mean, e_mean, n_max, e_max = torch.stack([ds.node_counts.double().mean(), ds.edge_counts.double().mean(),
                                                     ds.node_counts.max().double(), ds.edge_counts.max().double()]).tolist()
         capacity = (max(int(np.ceil(n_mean * slots)), int(n_max)) + 2, max(int(np.ceil(e_mean * slots)), int(e_max)))
-        replayed = G.ReplayedStep(gsat, ds, slots, capacity=capacity, ragged=True)
+        replayed = G.ReplayedStep(gsat, ds, slots, capacity=capacity, ragged=True, log_k=5 if args.train_scores else None)
         replayed_eval = G.ReplayedEval(gsat, ds, slots, 5, capacity=capacity, ragged=True)
     elif args.graph and n_train >= args.batch_size:
         replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
@@ -143,6 +151,7 @@ def main():
         perm = gen.permutation(n_train)
         tot, nb = 0.0, 0
         if args.ragged:
+            replayed.begin_epoch()                                # empties the training-pass log, when there is one
             for row in replayed.batches(perm):                    # every batch fits the capacity and is a replay; the tail included
                 tot, nb = tot + replayed.step(row, epoch), nb + 1
             if replayed.overflowed():
@@ -172,6 +181,10 @@ def main():
             acc, auc, prec = evaluate_replayed(test_ids, epoch) if replayed_eval is not None else evaluate(test_ids)
             print(f"epoch {epoch + 1:3d}  train loss {float(tot) / nb:.4f}  test acc {acc:.3f}  attention ROC-AUC vs motif edges {auc:.3f}  prec@5 {prec:.3f}",
                   flush=True)
+            if args.train_scores:                                 # scored from what the replays of this epoch logged: no eager batch
+                res = replayed.epoch_scores()
+                print(f"      train  loss {res['loss']:.4f}  pred {res['pred']:.4f}  info {res['info']:.4f}  acc {res['clf_acc']:.3f}  "
+                      f"clf ROC-AUC {res['clf_roc']:.3f}  attention ROC-AUC {res['att_auroc']:.3f}  prec@5 {res['precision@5']:.3f}", flush=True)
     if world > 1:
         dist.destroy_process_group()
 
