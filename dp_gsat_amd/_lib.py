@@ -128,11 +128,15 @@ SIGNATURES = {
     "gsat_subgraph_block_items": (I64, []),
     "gsat_subgraph_workspace_bytes": (SZ, [I64, I64]),
     "gsat_subgraph_index": (INT, [P, I64, I64, P, P, I64, P, INT, INT, INT, I64, I64, INT, P, P, P, P, P, P, P, P, SZ, P]),
+    "gsat_subgraph_padded": (INT, [P, I64, I64, P, I64, P, INT, INT, P, I64, I64, I64, P, P, P, P, P, P, P, SZ, P]),
     "gsat_gather_rows": (INT, [P, P, I64, I64, P, P]),
     "gsat_eval_log_append": (INT, [P] * 8 + [I64] * 4 + [P] * 8 + [I64] * 3 + [P]),
     "gsat_delta_kl_segments_chunk": (I64, []),
     "gsat_delta_kl_segments_workspace_bytes": (SZ, [I64, I64]),
     "gsat_delta_kl_segments": (INT, [P, P, P, I64, I64, I64, F64, P, P, SZ, P]),
+    "gsat_fidelity_append": (INT, [P, P, P, I64, I64, P, P, P, P, I64, P]),
+    "gsat_fidelity_reduce": (INT, [P, P, P, I64, P, P]),
+    "gsat_fidelity_reset": (INT, [P, P]),
 }
 
 

@@ -212,6 +212,18 @@ __device__ __forceinline__ float4 philox_keep4(uint64_t seed, int layer, int row
     return make_float4((float)(r.x >> 8) * k >= p ? 1.f : 0.f, (float)(r.y >> 8) * k >= p ? 1.f : 0.f,
                        (float)(r.z >> 8) * k >= p ? 1.f : 0.f, (float)(r.w >> 8) * k >= p ? 1.f : 0.f);
 }
+
+// Padding edge j of a fixed-capacity batch with N real nodes, n_pad >= 2 padding nodes behind them and e_pad padding edges -- the ONE
+// rule of gsat_collate_padded and gsat_subgraph_padded: pair q = j / 2 joins the padding nodes q % n_pad and (q + 1) % n_pad, forward in
+// the even slot and back in the odd one; an odd count ends in a self loop, so the padding set is symmetric whatever its size.
+__device__ __forceinline__ void padding_edge(int64_t N, int64_t n_pad, int64_t e_pad, int64_t j, int64_t& src, int64_t& dst) {
+    const int64_t q = j >> 1;
+    const int64_t a = N + q % n_pad, b = N + (q + 1) % n_pad;
+    const bool loop = j == e_pad - 1 && (e_pad & 1);
+    const bool fwd = (j & 1) == 0;
+    src = fwd ? a : b;
+    dst = loop ? a : (fwd ? b : a);
+}
 #endif
 
 }  // namespace gsat

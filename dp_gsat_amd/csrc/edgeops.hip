@@ -375,15 +375,11 @@ __global__ void k_collate_padded(const int64_t* __restrict__ ids, const int64_t*
             edge_index[i] = edge_local_all[slot] + off;
             edge_index[E_cap + i] = edge_local_all[E_all + slot] + off;
         } else {
-            // pair q joins padding nodes q % n_pad and (q + 1) % n_pad, forward in the even slot and back in the odd one; an odd
-            // count ends in a self loop, so the padding set is symmetric whatever its size
-            const int64_t n_pad = N_cap - N, e_pad = E_cap - E, j = i - E, q = j >> 1;
-            const int64_t a = N + q % n_pad, b = N + (q + 1) % n_pad;
-            const bool loop = j == e_pad - 1 && (e_pad & 1);
-            const bool fwd = (j & 1) == 0;
+            int64_t src, dst;                        // the padding rule (common.h), shared with gsat_subgraph_padded
+            padding_edge(N, N_cap - N, E_cap - E, i - E, src, dst);
             edge_src_slot[i] = -1;
-            edge_index[i] = fwd ? a : b;
-            edge_index[E_cap + i] = loop ? a : (fwd ? b : a);
+            edge_index[i] = src;
+            edge_index[E_cap + i] = dst;
         }
     }
 }

@@ -13,6 +13,10 @@
 //   edge mode, isolated nodes dropped     : clear marks -> edge flags + endpoint marks -> node counts -> scan -> node outputs
 //                                           -> edge outputs                                                                 (6)
 // The endpoint marks are byte stores of the value 1 (they race only with identical values); nothing is cleared by a memset node.
+//
+// gsat_subgraph_padded: the same passes into outputs of a CAPACITY shape -- the flags pass reads the counted nodes / edges of a padded
+// input from its valid word, the scan writes valid_out = (N', E', graphs, overflow), the two output passes emit the real part and one
+// more pass (k_subp_fill) turns the slack into the padding graph by the rule of gsat_collate_padded.  5 launches (7), no size read back.
 #include "common.h"
 #include <algorithm>
 
@@ -106,20 +110,22 @@ __global__ void __launch_bounds__(SUB_BLOCK) k_sub_clear(uint4* __restrict__ p, 
 // Workgroups [0, nb_nodes): node flags and counts.  node_src = the caller's node_keep (node mode), the endpoint marks (edge mode with
 // isolated nodes dropped; then node_src == node_flag and nothing is rewritten) or null (every node kept).
 // Workgroups [nb_nodes, ...): edge flags and counts.  Edge mode: flag = edge_keep != 0; node mode: both endpoints kept.  An edge with an
-// id outside [0, N) is dropped and reported in bad[workgroup]; `mark` (edge mode, drop_isolated) receives a 1 at both endpoints.
-__global__ void __launch_bounds__(SUB_BLOCK)
-k_sub_flags(const int64_t* __restrict__ ei, int64_t E, int64_t N, const uint8_t* __restrict__ edge_keep, const uint8_t* __restrict__ node_keep,
-            const uint8_t* node_src, uint8_t* node_flag, uint8_t* mark, int nb_nodes, uint8_t* __restrict__ edge_mask,
-            int32_t* __restrict__ cnt_n, int32_t* __restrict__ cnt_e, int32_t* __restrict__ bad) {
-    __shared__ int sh[SUB_BLOCK / 64];
+// id outside [0, Nv) is dropped and reported in bad[workgroup]; `mark` (edge mode, drop_isolated) receives a 1 at both endpoints.
+// N / E are the arrays' extents, Nv <= N / Ev <= E the counted items: a node row >= Nv or an edge slot >= Ev gets flag 0 and its keep
+// entry is never read (a padded input; otherwise Nv == N, Ev == E).
+__device__ __forceinline__ void sub_flags(const int64_t* __restrict__ ei, int64_t E, int64_t N, int64_t Ev, int64_t Nv,
+                                          const uint8_t* __restrict__ edge_keep, const uint8_t* __restrict__ node_keep,
+                                          const uint8_t* node_src, uint8_t* node_flag, uint8_t* mark, int nb_nodes,
+                                          uint8_t* __restrict__ edge_mask, int32_t* __restrict__ cnt_n, int32_t* __restrict__ cnt_e,
+                                          int32_t* __restrict__ bad, int* sh) {
     int total;
     if ((int)blockIdx.x < nb_nodes) {
         const int64_t i0 = (int64_t)blockIdx.x * SUB_ITEMS + (int64_t)threadIdx.x * SUB_IPT;
         uint32_t bits;
         if (node_src) {
-            bits = load_flags8(node_src, i0, N);
+            bits = load_flags8(node_src, i0, Nv);
         } else {
-            const int64_t left = N - i0;
+            const int64_t left = Nv - i0;
             bits = left >= SUB_IPT ? 0xFFu : (left > 0 ? (1u << left) - 1u : 0u);
         }
         if (node_src != node_flag) store_flags8(node_flag, i0, N, bits);
@@ -132,13 +138,13 @@ k_sub_flags(const int64_t* __restrict__ ei, int64_t E, int64_t N, const uint8_t*
     int64_t s[SUB_IPT], d[SUB_IPT];
     load_ids8(ei, i0, E, s);
     load_ids8(ei + E, i0, E, d);
-    const uint32_t want = edge_keep ? load_flags8(edge_keep, i0, E) : 0xFFu;
+    const uint32_t want = edge_keep ? load_flags8(edge_keep, i0, Ev) : 0xFFu;
     uint32_t bits = 0;
     int any_bad = 0;
 #pragma unroll
     for (int j = 0; j < SUB_IPT; ++j) {
-        if (i0 + j >= E) continue;
-        const bool in_range = (uint64_t)s[j] < (uint64_t)N && (uint64_t)d[j] < (uint64_t)N;
+        if (i0 + j >= Ev) continue;
+        const bool in_range = (uint64_t)s[j] < (uint64_t)Nv && (uint64_t)d[j] < (uint64_t)Nv;
         any_bad |= in_range ? 0 : 1;
         bool k = in_range && ((want >> j) & 1u);
         if (k && node_keep) k = node_keep[s[j]] != 0 && node_keep[d[j]] != 0;
@@ -151,6 +157,35 @@ k_sub_flags(const int64_t* __restrict__ ei, int64_t E, int64_t N, const uint8_t*
     (void)block_rank(bits, sh, total);
     any_bad = __syncthreads_or(any_bad);
     if (threadIdx.x == 0) { cnt_e[b] = total; bad[b] = any_bad ? 1 : 0; }
+}
+
+__global__ void __launch_bounds__(SUB_BLOCK)
+k_sub_flags(const int64_t* __restrict__ ei, int64_t E, int64_t N, const uint8_t* __restrict__ edge_keep, const uint8_t* __restrict__ node_keep,
+            const uint8_t* node_src, uint8_t* node_flag, uint8_t* mark, int nb_nodes, uint8_t* __restrict__ edge_mask,
+            int32_t* __restrict__ cnt_n, int32_t* __restrict__ cnt_e, int32_t* __restrict__ bad) {
+    __shared__ int sh[SUB_BLOCK / 64];
+    sub_flags(ei, E, N, E, N, edge_keep, node_keep, node_src, node_flag, mark, nb_nodes, edge_mask, cnt_n, cnt_e, bad, sh);
+}
+
+// The counts of a padded input: (N_real, E_real) of its valid word, clamped to the arrays; nothing of an input that overflowed.
+__device__ __forceinline__ void valid_counts(const int32_t* __restrict__ valid_in, int64_t N, int64_t E, int64_t& Nv, int64_t& Ev) {
+    Nv = N; Ev = E;
+    if (valid_in) {
+        const bool spoiled = valid_in[3] != 0;
+        Nv = spoiled ? 0 : min<int64_t>(max<int64_t>(valid_in[0], 0), N);
+        Ev = spoiled ? 0 : min<int64_t>(max<int64_t>(valid_in[1], 0), E);
+    }
+}
+
+// k_sub_flags with the counted nodes / edges read from valid_in (int32[4], nullable) on the device
+__global__ void __launch_bounds__(SUB_BLOCK)
+k_subp_flags(const int64_t* __restrict__ ei, int64_t E, int64_t N, const int32_t* __restrict__ valid_in, const uint8_t* __restrict__ edge_keep,
+             const uint8_t* __restrict__ node_keep, const uint8_t* node_src, uint8_t* node_flag, uint8_t* mark, int nb_nodes,
+             uint8_t* __restrict__ edge_mask, int32_t* __restrict__ cnt_n, int32_t* __restrict__ cnt_e, int32_t* __restrict__ bad) {
+    __shared__ int sh[SUB_BLOCK / 64];
+    int64_t Nv, Ev;
+    valid_counts(valid_in, N, E, Nv, Ev);
+    sub_flags(ei, E, N, Ev, Nv, edge_keep, node_keep, node_src, node_flag, mark, nb_nodes, edge_mask, cnt_n, cnt_e, bad, sh);
 }
 
 // exclusive scan of a[0 .. n) in place by the one workgroup; returns the total in every thread
@@ -284,6 +319,51 @@ k_sub_edge_out(const int64_t* __restrict__ ei, int64_t E, int64_t N, const uint8
     }
 }
 
+// k_sub_scan for a padded result: the workgroup offsets and valid_out = (N', E', graphs, overflow).  The result
+// overflows when fewer than two padding nodes would remain, the edges do not fit, the input had overflowed or an edge had a bad id:
+// valid_out = (0, 0, 0, 1) and k_subp_fill makes every row and slot padding.
+__global__ void __launch_bounds__(SUB_SCAN_BLOCK)
+k_subp_scan(int32_t* __restrict__ cnt_n, int nb_nodes, int32_t* __restrict__ cnt_e, int nb_edges, const int32_t* __restrict__ bad,
+            int64_t cap_nodes, int64_t cap_edges, const int32_t* __restrict__ valid_in, int64_t G, int32_t* __restrict__ valid_out) {
+    __shared__ int sh[SUB_SCAN_BLOCK / 64];
+    const int kept_n = scan_counts(cnt_n, nb_nodes, sh);
+    const int kept_e = scan_counts(cnt_e, nb_edges, sh);
+    int any_bad = 0;
+    for (int i = threadIdx.x; i < nb_edges; i += SUB_SCAN_BLOCK) any_bad |= bad[i];
+    any_bad = __syncthreads_or(any_bad);
+    if (threadIdx.x == 0) {
+        // the entry behind the offsets is where k_sub_node_out / k_sub_edge_out start their filler (valid ids behind the true count);
+        // here k_subp_fill owns everything behind the counts, so the start is put at the capacity and that loop writes nothing
+        cnt_n[nb_nodes] = (int32_t)cap_nodes;
+        cnt_e[nb_edges] = (int32_t)cap_edges;
+        const bool over = (int64_t)kept_n + 2 > cap_nodes || (int64_t)kept_e > cap_edges || any_bad || (valid_in && valid_in[3] != 0);
+        valid_out[0] = over ? 0 : kept_n;
+        valid_out[1] = over ? 0 : kept_e;
+        valid_out[2] = over ? 0 : (valid_in ? valid_in[2] : (int32_t)G);
+        valid_out[3] = over ? 1 : 0;
+    }
+}
+
+// The slack of a padded result, in the style of k_collate_padded: thread i takes node row i and edge slot i and reads the counts from
+// valid_out.  Rows >= N' become padding nodes (graph pad_graph, node_id -1), slots >= E' padding edges among them (edge_id -1).
+__global__ void k_subp_fill(const int32_t* __restrict__ valid_out, int64_t cap_nodes, int64_t cap_edges, int64_t pad_graph,
+                            int64_t* __restrict__ node_id, int64_t* __restrict__ new_batch, int64_t* __restrict__ edge_id,
+                            int64_t* __restrict__ new_ei) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t N = valid_out[0], E = valid_out[1];
+    if (i < cap_nodes && i >= N) {
+        node_id[i] = -1;
+        if (new_batch) new_batch[i] = pad_graph;
+    }
+    if (i < cap_edges && i >= E) {
+        int64_t src, dst;
+        padding_edge(N, cap_nodes - N, cap_edges - E, i - E, src, dst);
+        edge_id[i] = -1;
+        new_ei[i] = src;
+        new_ei[cap_edges + i] = dst;
+    }
+}
+
 // out unit u = table unit index[u / U] * U + u % U, a unit being one T (16, 8, 4 or 1 bytes) and U the units per row
 template <class T, class I>
 __global__ void __launch_bounds__(256) k_gather_rows(const T* __restrict__ table, const int64_t* __restrict__ index, I total, I U,
@@ -391,6 +471,66 @@ int gsat_subgraph_index(const int64_t* edge_index, int64_t E, int64_t N, const i
             GSAT_LAUNCH_CHECK();
         }
     }
+    return GSAT_OK;
+}
+
+int gsat_subgraph_padded(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* batch, int64_t G, const uint8_t* keep, int mode,
+                         int drop_isolated, const int32_t* valid_in, int64_t pad_graph, int64_t cap_nodes, int64_t cap_edges,
+                         int64_t* node_id, int64_t* edge_id, int64_t* new_edge_index, int64_t* new_batch, uint8_t* edge_mask,
+                         int32_t* valid_out, void* workspace, size_t ws_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(E >= 0 && N >= 0 && G >= 0 && pad_graph >= 0 && (mode == 0 || mode == 1) && cap_nodes >= 2 && cap_edges >= 0, GSAT_ERR_ARG,
+                 "gsat_subgraph_padded: bad argument (two padding nodes always remain)");
+    GSAT_REQUIRE(N < (1ll << 31) && E < (1ll << 31) && G < (1ll << 31) && pad_graph < (1ll << 31) && cap_nodes < (1ll << 31) &&
+                 cap_edges < (1ll << 31), GSAT_ERR_UNSUPPORTED, "gsat_subgraph_padded: >2^31 entries");
+    GSAT_REQUIRE(valid_out && node_id && (E == 0 || (edge_index && edge_mask)) && (mode == 0 ? (E == 0 || keep) : (N == 0 || keep)) &&
+                 (cap_edges == 0 || (edge_id && new_edge_index)) && (!batch || new_batch), GSAT_ERR_ARG,
+                 "gsat_subgraph_padded: null pointer");
+    const SubLayout lay(N, E);
+    Arena ar(workspace, ws_bytes);
+    uint8_t* node_flag = ar.take<uint8_t>(lay.flag_bytes);
+    int32_t* node_rank = ar.take<int32_t>((size_t)N + 1);
+    int32_t* cnt_n = ar.take<int32_t>((size_t)lay.nb_nodes + 1);
+    int32_t* cnt_e = ar.take<int32_t>((size_t)lay.nb_edges + 1);
+    int32_t* bad = ar.take<int32_t>((size_t)lay.nb_edges + 1);
+    GSAT_REQUIRE(ar.ok() && bad, GSAT_ERR_WORKSPACE, "gsat_subgraph_padded: workspace %zu < %zu", ws_bytes, ar.off);
+    const int nbn = lay.nb_nodes, nbe = lay.nb_edges;
+    if (mode == 0 && drop_isolated) {
+        if (N > 0) {
+            const int64_t n16 = (int64_t)(lay.flag_bytes / 16);
+            k_sub_clear<<<(unsigned)ceil_div(n16, SUB_BLOCK), SUB_BLOCK, 0, stream>>>(reinterpret_cast<uint4*>(node_flag), n16);
+            GSAT_LAUNCH_CHECK();
+        }
+        if (nbe > 0) {
+            k_subp_flags<<<nbe, SUB_BLOCK, 0, stream>>>(edge_index, E, N, valid_in, keep, nullptr, nullptr, nullptr, node_flag, 0, edge_mask,
+                                                        cnt_n, cnt_e, bad);
+            GSAT_LAUNCH_CHECK();
+        }
+        if (nbn > 0) {
+            k_subp_flags<<<nbn, SUB_BLOCK, 0, stream>>>(edge_index, E, N, valid_in, nullptr, nullptr, node_flag, node_flag, nullptr, nbn,
+                                                        edge_mask, cnt_n, cnt_e, bad);
+            GSAT_LAUNCH_CHECK();
+        }
+    } else if (nbn + nbe > 0) {
+        const uint8_t* node_keep = mode == 1 ? keep : nullptr;
+        k_subp_flags<<<nbn + nbe, SUB_BLOCK, 0, stream>>>(edge_index, E, N, valid_in, mode == 0 ? keep : nullptr, node_keep, node_keep,
+                                                          node_flag, nullptr, nbn, edge_mask, cnt_n, cnt_e, bad);
+        GSAT_LAUNCH_CHECK();
+    }
+    k_subp_scan<<<1, SUB_SCAN_BLOCK, 0, stream>>>(cnt_n, nbn, cnt_e, nbe, bad, cap_nodes, cap_edges, valid_in, G, valid_out);
+    GSAT_LAUNCH_CHECK();
+    // the real part, as gsat_subgraph_index emits it (never at or beyond the capacities); k_subp_fill then owns everything behind the
+    // counts of valid_out -- all of it after an overflow
+    k_sub_node_out<<<std::max(nbn, 1), SUB_BLOCK, 0, stream>>>(node_flag, N, cnt_n, nbn, batch, cap_nodes, node_id, new_batch, node_rank);
+    GSAT_LAUNCH_CHECK();
+    if (nbe > 0) {
+        k_sub_edge_out<<<nbe, SUB_BLOCK, 0, stream>>>(edge_index, E, N, edge_mask, cnt_e, nbe, node_rank, cap_edges, edge_id, new_edge_index,
+                                                      nullptr, 0, nullptr);
+        GSAT_LAUNCH_CHECK();
+    }
+    k_subp_fill<<<(unsigned)ceil_div(std::max(cap_nodes, cap_edges), SUB_BLOCK), SUB_BLOCK, 0, stream>>>(valid_out, cap_nodes, cap_edges, pad_graph,
+                                                                                                      node_id, new_batch, edge_id, new_edge_index);
+    GSAT_LAUNCH_CHECK();
     return GSAT_OK;
 }
 

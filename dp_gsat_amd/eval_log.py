@@ -197,3 +197,73 @@ class EpochLog:
         curve.update(precision=fl[10:10 + B].copy(), recall=fl[10 + B:10 + 2 * B].copy())
         res["pr_curve"] = curve
         return res
+
+
+class FidelityLog:
+    """``FidelityLog(max_graphs, classes, device=None)``: the device log of explanation fidelity (csrc/fidelity.hip), allocated once.
+    ``append`` takes the logits of the backbone on the full batch, on the explanation alone and on the batch without the explanation and
+    keeps, per graph, the three predicted classes (``cls int32[max_graphs, 3]``) and the probabilities of the class predicted from the
+    full batch (``p float64[max_graphs, 3]``); ``state`` int64[4] = (graphs, batches, flags, 0) lives on the device.  ``append`` is two
+    kernel launches and reads nothing, so it replays inside a captured graph (``ReplayedFidelity``).  An append that cannot be taken -- a
+    padded batch whose overflow word is set (flag bit 0), or one that would exceed ``max_graphs`` (flag bit 1) -- writes nothing but
+    its flag and is reported by ``compute``."""
+
+    def __init__(self, max_graphs: int, classes: int, device=None):
+        if int(max_graphs) < 0 or int(classes) < 1:
+            raise ValueError("FidelityLog needs a non-negative capacity and at least one logit column")
+        if int(max_graphs) >= 2 ** 31:
+            raise ValueError("FidelityLog: max_graphs must be below 2**31")
+        self.max_graphs, self.classes = int(max_graphs), int(classes)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise GsatHipError("dp_gsat_amd.eval_log needs a ROCm (cuda) device: the HIP path has no CPU fallback")
+        self.cls = torch.empty((self.max_graphs, 3), dtype=torch.int32, device=dev)
+        self.p = torch.empty((self.max_graphs, 3), dtype=torch.float64, device=dev)
+        self.state = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._out = torch.empty(10, dtype=torch.int64, device=dev)
+
+    def reset(self) -> None:
+        """Empty the log: one kernel zeroes ``state`` (no memset node, so a captured graph may hold it), nothing is read."""
+        call("gsat_fidelity_reset", ptr(self.state), stream())
+
+    def append(self, logits_full, logits_keep, logits_drop, valid=None) -> None:
+        """Log one batch: three fp32 blocks ``[G_rows, classes]``.  ``valid``: the int32[4] word of a padded batch -- the first
+        ``clamp(valid[2], 0, G_rows)`` rows are logged and the others never loaded; without it every row."""
+        blocks = []
+        for t in (logits_full, logits_keep, logits_drop):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise GsatHipError("dp_gsat_amd.eval_log needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+            if t.dim() != 2 or int(t.shape[1]) != self.classes:
+                raise ValueError(f"logits must have shape [G, {self.classes}]")
+            blocks.append(t.detach().to(torch.float32).contiguous())
+        rows = int(blocks[0].shape[0])
+        if any(int(t.shape[0]) != rows for t in blocks):
+            raise ValueError("the three logit blocks must have one row per graph of the same batch")
+        if valid is not None:
+            if not isinstance(valid, torch.Tensor) or valid.dtype != torch.int32 or valid.numel() < 4 or not valid.is_cuda:
+                raise ValueError("valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+            valid = valid.contiguous()
+        some = lambda t: ptr(t) if t.numel() else None
+        call("gsat_fidelity_append", some(blocks[0]), some(blocks[1]), some(blocks[2]), rows, self.classes,
+             ptr(valid) if valid is not None else None, some(self.cls), some(self.p), ptr(self.state), self.max_graphs, stream())
+
+    def compute(self) -> dict:
+        """Score everything logged since ``reset``, with ONE reduction launch and ONE host read: ``fidelity_plus = mean(p_full - p_drop)``,
+        ``fidelity_minus = mean(p_full - p_keep)``, the means ``p_full / p_keep / p_drop``, the exact flip rates ``flip_plus = #(cls_drop !=
+        cls_full) / n`` and ``flip_minus = #(cls_keep != cls_full) / n``, and ``n``.  fp64 sums in a fixed order: two runs over the same log
+        are bitwise equal.  ValueError when an append was refused, or nothing was appended."""
+        some = lambda t: ptr(t) if t.numel() else None
+        call("gsat_fidelity_reduce", some(self.cls), some(self.p), ptr(self.state), self.max_graphs, ptr(self._out), stream())
+        packed = self._out.cpu().numpy()                                                        # the one host read
+        n, batches, flags, flips_plus, flips_minus = (int(v) for v in packed[:5])
+        if flags & FLAG_OVERFLOW:
+            raise ValueError("FidelityLog: flag bit 0 is set -- a padded batch did not fit its capacity (valid[3]) and was not logged")
+        if flags & FLAG_FULL:
+            raise ValueError(f"FidelityLog: flag bit 1 is set -- an append would have exceeded max_graphs ({self.max_graphs}) and was "
+                             "not logged")
+        if batches == 0 or n == 0:
+            raise ValueError("FidelityLog.compute() before any append()")
+        sums = packed[5:10].view(np.float64)
+        return {"fidelity_plus": float(sums[0]) / n, "fidelity_minus": float(sums[1]) / n, "p_full": float(sums[2]) / n,
+                "p_keep": float(sums[3]) / n, "p_drop": float(sums[4]) / n, "flip_plus": flips_plus / n, "flip_minus": flips_minus / n,
+                "n": n}

@@ -57,10 +57,18 @@ def _segments(edge_index, batch, num_graphs):
     return get_index(edge_index, int(batch.shape[0])).graphs(batch, num_graphs)
 
 
-def _rank(att, edge_index, batch, num_graphs, path, k=0, label=None, want=("order", "rank")):
-    """One gsat_rank_edges call; returns (dict of the wanted outputs, GraphSegments)."""
+def _rank(att, edge_index, batch, num_graphs, path, k=0, label=None, want=("order", "rank"), max_seg_edges=None, ranked_graphs=None):
+    """One gsat_rank_edges call; returns (dict of the wanted outputs, GraphSegments).  ``max_seg_edges``: the caller's bound on the
+    largest graph, in place of the one the batch index may have to read back -- the fused path is then taken whatever the mode, and a
+    bound above ``rank_edges_lds_cap()`` is a ValueError.  ``ranked_graphs`` (with ``max_seg_edges`` only): only the first so many graphs
+    are ranked; the entries of the other graphs' edges are not written."""
     if path not in _PATHS:
         raise ValueError(f"path must be one of {sorted(_PATHS)}")
+    if ranked_graphs is not None and max_seg_edges is None:
+        # the radix path sorts every edge slot and would rank the unranked graphs' edges inside the last ranked graph
+        raise ValueError("ranked_graphs is defined on the fused ranking only: give max_seg_edges (a bound on the edges of one graph) with it")
+    if max_seg_edges is not None and _PATHS[path] == 2:
+        raise ValueError("max_seg_edges declares a bound for the fused ranking: it does not go with path='general'")
     a = _att(att)
     seg = _segments(edge_index, batch, num_graphs)
     E, G, dev = seg.index.E, seg.G, a.device
@@ -79,6 +87,16 @@ def _rank(att, edge_index, batch, num_graphs, path, k=0, label=None, want=("orde
         out["hits"] = torch.empty(G, dtype=torch.int32, device=dev)
     max_seg = seg.max_edges_per_graph                      # -1: unknown and not to be read back now -> general path
     code = _PATHS[path]
+    if max_seg_edges is not None:
+        max_seg = int(max_seg_edges)
+        if not 0 <= max_seg <= rank_edges_lds_cap():
+            raise ValueError(f"max_seg_edges = {max_seg} is outside [0, rank_edges_lds_cap() = {rank_edges_lds_cap()}]: the fused "
+                             "ranking cannot take it, and a declared bound never changes the path silently")
+        code = 1
+    if ranked_graphs is not None:
+        if not 0 <= int(ranked_graphs) <= G:
+            raise ValueError(f"ranked_graphs = {ranked_graphs} outside [0, {G}]")
+        G = int(ranked_graphs)
     fused = code == 1 or (code == 0 and 0 <= max_seg <= rank_edges_lds_cap())
     ws, ws_bytes = None, 0
     if not fused:
@@ -105,14 +123,22 @@ def rank_edges(att, edge_index, batch, num_graphs: Optional[int] = None, path: s
 
 
 def topk_edge_mask(att, edge_index, batch, k: Optional[int] = None, ratio: Optional[float] = None, num_graphs: Optional[int] = None,
-                   path: str = "auto") -> torch.Tensor:
-    """bool[E]: the ``k`` best edges of every graph, or its ``ceil(ratio * E_g)`` best."""
+                   path: str = "auto", *, max_seg_edges: Optional[int] = None, ranked_graphs: Optional[int] = None) -> torch.Tensor:
+    """bool[E]: the ``k`` best edges of every graph, or its ``ceil(ratio * E_g)`` best.
+
+    ``max_seg_edges`` (keyword only): a bound on the edges of one graph that the caller knows, e.g. from its dataset.  The ranking then
+    runs the fused one-launch path also in sync-free mode and inside a stream capture, where the batch's own largest graph is unknown;
+    a bound above ``rank_edges_lds_cap()`` raises ValueError.  ``ranked_graphs`` (keyword only): rank the first so many graphs only --
+    for a padded batch its ``num_graphs - 1``, so that the padding graph is not ranked at all; only the fused path can leave graphs out, so
+    it needs ``max_seg_edges`` (ValueError without it, or with ``path="general"``).  The mask's entries at the edges of the
+    other graphs are then NOT written (arbitrary bytes): ``edge_subgraph_padded`` never reads them."""
     if (k is None) == (ratio is None):
         raise ValueError("give exactly one of k and ratio")
+    bound = dict(max_seg_edges=max_seg_edges, ranked_graphs=ranked_graphs)
     if k is not None:
-        out, _ = _rank(att, edge_index, batch, num_graphs, path, k=k, want=("topk",))
+        out, _ = _rank(att, edge_index, batch, num_graphs, path, k=k, want=("topk",), **bound)
         return out["topk"].bool()
-    out, seg = _rank(att, edge_index, batch, num_graphs, path, want=("rank",))
+    out, seg = _rank(att, edge_index, batch, num_graphs, path, want=("rank",), **bound)
     eptr, _, eg, _ = seg.edge_segments
     keep = torch.ceil((eptr[1:] - eptr[:-1]).double() * float(ratio)).to(torch.int32)
     return out["rank"] < keep[eg]

@@ -4,23 +4,27 @@ A captured step bakes N, E and G into every launch, and real batches differ in N
 every batch to a fixed capacity (PackedDataset.collate_padded) inside the captured graph, so that a step is: copy the graph ids, set
 r, replay.  The padding is arithmetically inert.
 
-The four public classes say what their graphs hold (``run_once``) and what they refuse; the protocol around it -- static inputs, warm-up
+The public classes say what their graphs hold (``run_once``) and what they refuse; the protocol around it -- static inputs, warm-up
 on a side stream, capture, putting everything back, ``step`` -- is ``_Replayed`` and the module's functions, each written once.
 """
 from __future__ import annotations
 
+import math
 from contextlib import contextmanager
 from typing import Optional
 
 import torch
 
+from . import explain as _explain
 from ._lib import call, ptr, stream
 from .collate import collate_padded_pair
-from .eval_log import EpochLog
+from .eval_log import EpochLog, FidelityLog
 from .evaluate import MAX_BINS
-from .graph_index import clear_cache, set_sync_free, sync_free
+from .graph_index import clear_cache, get_index, set_sync_free, sync_free
 from .gsat import get_r
 from .ops import edge_tensor
+from .padding import padded
+from .subgraph import edge_subgraph_padded
 
 _MULTI_LABEL = "a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)"
 
@@ -116,7 +120,7 @@ def _first_budget_row(dataset, capacity, batch_size, dual=None):
 
 
 class _Replayed:
-    """What the four classes share: the static inputs of the captured graphs (``graph_ids``, ``r``), the warm-up-and-capture driver and
+    """What the replay classes share: the static inputs of the captured graphs (``graph_ids``, ``r``), the warm-up-and-capture driver and
     ``step``.  A class with one graph is the pair (unmixed, mixed) without its mixed half.  A subclass gives ``run_once`` -- the body a
     graph holds, which ends in ``_publish`` -- and says in its constructor what it refuses."""
 
@@ -745,3 +749,132 @@ class ReplayedDualEval(_Replayed):
         ``dual_avg_bkg_att_weights`` of the dual attention.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
         self._set_seed_state(int(epoch) << 32)
         return _run_epoch(self, graph_ids, epoch)
+
+
+# ---- explanation fidelity ---------------------------------------------------------------------------------------------------------------------
+def keep_capacity(E_cap: int, batch_size: int, k: Optional[int] = None, ratio: Optional[float] = None) -> int:
+    """The edge capacity of the explanation side of a fidelity batch, derived and not tuned: ``k * batch_size`` for a top-k of ``k`` edges
+    per graph; ``min(E_cap, ceil(ratio * E_cap) + batch_size)`` for a ratio, because ``sum_g ceil(ratio * E_g) <= ratio * sum_g E_g +
+    batch_size``.  A batch that fits ``E_cap`` can therefore never overflow the explanation side."""
+    if (k is None) == (ratio is None):
+        raise ValueError("give exactly one of k and ratio")
+    if k is not None:
+        return int(k) * int(batch_size)
+    return min(int(E_cap), int(math.ceil(float(ratio) * int(E_cap))) + int(batch_size))
+
+
+class ReplayedFidelity(_Replayed):
+    """``ReplayedFidelity(gsat, dataset, batch_size, k=None, ratio=None, capacity=None, max_graphs=None, graph=None, ragged=False)``: the
+    fidelity of the top-k (or top-ratio) explanation over ``dataset`` -- the one explanation score that needs no edge labels -- as replays of
+    ONE captured hipGraph.  A replay holds clear_cache; ``collate_padded``; the eval-mode attention on the edges, ``gsat.forward_pass(b, 0,
+    False)[0]``, under ``torch.no_grad()`` with every module in ``eval()`` mode; ``topk_edge_mask`` on the fused one-launch path over the
+    ``batch_size`` real graphs with the dataset's largest edge count as its bound; two padded extractions -- ``keep =
+    edge_subgraph_padded(b, mask, (N_cap, E_keep_cap))`` and ``drop = edge_subgraph_padded(b, ~mask, (N_cap, E_cap))`` --; three
+    ``gsat.clf`` forwards WITHOUT ``edge_atten``, each inside ``padded(valid, capacity)`` of its own batch; and ``log.append`` into a
+    :class:`~dp_gsat_amd.eval_log.FidelityLog` (``log``).  Nothing is read back per batch.
+
+    ``E_keep_cap`` is ``keep_capacity(E_cap, batch_size, k, ratio)``: derived, so that a batch that fits ``capacity`` never overflows the
+    explanation side, and tight, so that the padding graph of the explanation batch stays small.
+
+    ``run(graph_ids)`` resets the log, replays every full batch -- ragged: every row of ``batches``, no eager batch --, runs a fixed-count
+    tail eagerly through the same code on ``dataset.collate`` output, and returns ``log.compute()``: ``fidelity_plus``, ``fidelity_minus``,
+    ``p_full``, ``p_keep``, ``p_drop``, ``flip_plus``, ``flip_minus``, ``n``.
+
+    After a step: ``edge_att`` [E_cap, 1], ``topk`` bool[E_cap] (arbitrary at the padding slots), ``keep_batch``, ``drop_batch``,
+    ``logits_full`` / ``logits_keep`` / ``logits_drop`` [B + 1, C] and ``batch``.  ``overflowed()`` tells (one host read) whether a batch or
+    an extraction since the last call did not fit; ``check_epoch`` tells beforehand.
+
+    The graph writes no parameter, buffer or optimizer state and draws from neither the device seed stream nor torch's generators: a
+    fidelity epoch between ``ReplayedStep`` steps leaves the training run bitwise unchanged.
+
+    Refused with ValueError before anything is captured: both or neither of ``k`` and ``ratio``; a dataset without graph labels (edge
+    labels are NOT needed); ``DualGSAT``; ``sync_group`` BatchNorm; the multi-label criterion; a dataset whose largest graph has more
+    edges than ``rank_edges_lds_cap()`` (the radix ranking is not captured); a capacity the first batch does not fit."""
+
+    def __init__(self, gsat, dataset, batch_size: int, k: Optional[int] = None, ratio: Optional[float] = None,
+                 capacity: Optional[tuple] = None, max_graphs: Optional[int] = None, graph=None, ragged: bool = False):
+        if (k is None) == (ratio is None):
+            raise ValueError("give exactly one of k and ratio")
+        if k is not None and (isinstance(k, bool) or int(k) != k or int(k) < 1):
+            raise ValueError("k must be a positive int")
+        if ratio is not None and not 0.0 < float(ratio) <= 1.0:
+            raise ValueError("ratio must lie in (0, 1]")
+        if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
+            raise ValueError("ReplayedFidelity replays GSAT.forward_pass and its backbone; DualGSAT fidelity is not covered")
+        if getattr(gsat.criterion, "multi_label", False):
+            raise ValueError(_MULTI_LABEL)
+        _refuse_sync_group(gsat)
+        if dataset.y_all is None:
+            raise ValueError("ReplayedFidelity needs a dataset with graph labels (the eval-mode forward takes them); edge labels are not needed")
+        self.max_seg_edges = int(dataset.edge_counts.max()) if dataset.num_graphs else 0          # one host read, here
+        if self.max_seg_edges > _explain.rank_edges_lds_cap():
+            raise ValueError(f"the dataset's largest graph has {self.max_seg_edges} edges, above rank_edges_lds_cap() = "
+                             f"{_explain.rank_edges_lds_cap()}: the captured top-k takes the fused ranking only")
+        self.gsat, self.dataset = gsat, dataset
+        self.k, self.ratio = (None if k is None else int(k)), (None if ratio is None else float(ratio))
+        self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
+        N_cap, E_cap = self.capacity
+        self.keep_capacity = (N_cap, keep_capacity(E_cap, self.batch_size, self.k, self.ratio))
+        self._max_graphs = dataset.num_graphs if max_graphs is None else int(max_graphs)
+        self._overflow = torch.zeros(1, dtype=torch.int32, device=dataset.x_all.device)
+        self.log = self.batch = self.edge_att = self.topk = self.keep_batch = self.drop_batch = None
+        self.logits_full = self.logits_keep = self.logits_drop = None
+        try:
+            _capture_evaluator(self, self._make_log)
+        finally:
+            self._overflow.zero_()
+
+    def _make_log(self):
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        with torch.no_grad(), padded(b.valid, b.capacity):
+            get_index(b.edge_index, int(b.x.shape[0])).graphs(b.batch, int(b.num_graphs))
+            logits = self.gsat.clf(b.x, b.edge_index, b.batch, getattr(b, "edge_attr", None))
+        self.log = FidelityLog(self._max_graphs, int(logits.shape[1]), self.dataset.x_all.device)
+
+    def _forward(self, b, epoch=0):
+        """Attention, top-k, the two extractions, the three backbone forwards and the append for batch ``b`` -- a ``PaddedBatch`` (the
+        captured body) or ``collate`` output (the eager tail); the modules are in eval mode."""
+        clf = self.gsat.clf
+        with torch.no_grad():
+            att = edge_tensor(self.gsat.forward_pass(b, epoch, False)[0]).detach()
+            valid = getattr(b, "valid", None)
+            real = int(b.num_graphs) - (1 if valid is not None else 0)
+            mask = _explain.topk_edge_mask(att, b.edge_index, b.batch, k=self.k, ratio=self.ratio, num_graphs=int(b.num_graphs),
+                                           max_seg_edges=self.max_seg_edges, ranked_graphs=real)
+            keep = edge_subgraph_padded(b, mask, self.keep_capacity)
+            drop = edge_subgraph_padded(b, ~mask, self.capacity)
+            logits = []
+            for d in (b, keep, drop):
+                get_index(d.edge_index, int(d.x.shape[0])).graphs(d.batch, int(d.num_graphs))
+                if getattr(d, "valid", None) is None:
+                    logits.append(clf(d.x, d.edge_index, d.batch, getattr(d, "edge_attr", None)))
+                else:
+                    with padded(d.valid, d.capacity):
+                        logits.append(clf(d.x, d.edge_index, d.batch, getattr(d, "edge_attr", None)))
+            over = keep.valid[3:4] | drop.valid[3:4]
+            self._overflow.bitwise_or_(over if valid is None else over | valid[3:4])
+            if valid is None:       # the eager tail: its extractions have raised if they did not fit; the padding graph's row is cut off
+                logits = [z[:real] for z in logits]
+            self.log.append(*logits, valid)
+        return att, mask, keep, drop, logits
+
+    def run_once(self):
+        """The body of the captured graph, run on the current stream."""
+        clear_cache()
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        b.r = self.r
+        att, mask, keep, drop, logits = self._forward(b, 0)
+        self._publish(False, batch=b, edge_att=att, topk=mask, keep_batch=keep, drop_batch=drop, logits_full=logits[0],
+                      logits_keep=logits[1], logits_drop=logits[2])
+
+    def run(self, graph_ids, epoch: int = 0) -> dict:
+        """One fidelity epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, a
+        fixed-count tail of fewer than ``batch_size`` graphs runs eagerly through the same code (``dataset.collate``, then the padded
+        extractions at the captured capacities), and ``log.compute()`` -- one reduction launch, one host read -- gives the scores.
+        Ragged: the ids are packed by ``batches`` and every batch is a replay."""
+        return _run_epoch(self, graph_ids, epoch)
+
+    def overflowed(self) -> bool:
+        """True if a batch or an extraction since the last call (or since capture) did not fit its capacity.  One host read; clears the
+        flag."""
+        return _take_overflow(self)

@@ -8,6 +8,10 @@ attribute (csrc/subgraph.hip); kept nodes and edges stay in their original order
 Why a compacted graph and not a hard 0/1 ``edge_atten``: for GIN / GINE (a masked sum) the two are the same thing, for
 ``PNAConvSimple`` they are not -- a message scaled by 0 still enters ``mean``, ``min``, ``max``, ``std`` and the in-degree.  Fidelity of
 a PNA model therefore needs the graph WITHOUT the edges (:func:`explanation_fidelity`).
+
+:func:`edge_subgraph_padded` / :func:`node_subgraph_padded` extract into a batch of a fixed capacity (a ``PaddedBatch``: the kept part
+first, the slack as the padding graph, the counts in ``valid`` on the device): no size is needed from the host, so the extraction
+replays inside a captured graph (``ReplayedFidelity``).
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import GsatHipError, call, ptr, stream
+from .collate import PaddedBatch, _take_padded
 from .explain import topk_edge_mask
 from .graph_index import call_size, get_index, sync_free
 from .synth import Batch
@@ -173,6 +178,122 @@ def node_subgraph(data, node_keep: torch.Tensor, sizes: Optional[Tuple[int, int]
         mask[node_keep.reshape(-1)] = 1
         node_keep = mask
     return _extract(data, node_keep, 1, False, sizes)
+
+
+class PaddedSubgraphBatch(PaddedBatch):
+    """The extracted batch of :func:`edge_subgraph_padded` / :func:`node_subgraph_padded`: a ``PaddedBatch`` of the declared ``capacity``
+    -- kept nodes and edges first, the slack as the padding graph ``num_graphs - 1`` -- with ``valid`` (int32[4] on the device: N', E',
+    graphs, overflow), ``node_id int64[N_cap]`` / ``edge_id int64[E_cap]`` (old ids, ascending, -1 for padding), ``edge_mask bool[E]`` over
+    the ORIGINAL edge slots and ``y`` unchanged."""
+
+    def check(self) -> "PaddedSubgraphBatch":
+        """One host read of ``valid``: raises ValueError when the extraction overflowed (the batch is then all padding)."""
+        if int(self.valid[3]):
+            raise ValueError(_overflow_text(self.capacity))
+        return self
+
+
+def _overflow_text(capacity) -> str:
+    return (f"the extraction does not fit the capacity (N_cap, E_cap) = {tuple(capacity)} (two padding nodes must remain), its input "
+            "had overflowed, or edge_index contains node ids outside [0, num_nodes)")
+
+
+def _extract_padded(data, keep: torch.Tensor, mode: int, drop_isolated: bool, capacity) -> PaddedSubgraphBatch:
+    x, edge_index, batch = data.x, data.edge_index, data.batch
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    N, E, dev = int(x.shape[0]), int(edge_index.shape[1]), edge_index.device
+    if batch.dtype != torch.int64 or batch.dim() != 1 or int(batch.shape[0]) != N:
+        raise ValueError("batch must be an int64 vector with one entry per node")
+    what = "edge_keep" if mode == 0 else "node_keep"
+    if keep.numel() != (E if mode == 0 else N):
+        raise ValueError(f"{what} has {keep.numel()} entries for {E if mode == 0 else N}")
+    N_cap, E_cap = int(capacity[0]), int(capacity[1])
+    if N_cap < 2 or E_cap < 0:
+        raise ValueError("a padded extraction needs a capacity of at least two nodes (the padding nodes)")
+    _need_cuda(x, edge_index, batch, keep)
+    keep = _keep_u8(keep, E if mode == 0 else N, what)
+    valid_in = getattr(data, "valid", None)
+    if valid_in is not None:
+        if valid_in.dtype != torch.int32 or valid_in.numel() < 4 or not valid_in.is_cuda:
+            raise ValueError("data.valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+        valid_in = valid_in.contiguous()
+        num_graphs = int(data.num_graphs)                    # the input's own padding graph stays the padding graph
+        real_graphs = num_graphs - 1
+    else:
+        real_graphs = getattr(data, "num_graphs", None)
+        if real_graphs is None:
+            if sync_free() or torch.cuda.is_current_stream_capturing():
+                raise ValueError("a padded extraction of a batch without num_graphs would read batch.max() back")
+            real_graphs = int(batch.max().item()) + 1 if N else 0
+        real_graphs = int(real_graphs)
+        num_graphs = real_graphs + 1
+    ei, batch = edge_index.contiguous(), batch.contiguous()
+    # every real node kept at the input's own shape: rows and graph ids are the input's, padding rows included
+    shares_nodes = mode == 0 and not drop_isolated and valid_in is not None and N_cap == N
+    ws_bytes = max(call_size("gsat_subgraph_workspace_bytes", N, E), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    edge_mask = torch.empty(E, dtype=torch.uint8, device=dev)
+    valid = torch.empty(4, dtype=torch.int32, device=dev)
+    node_id = torch.empty(N_cap, dtype=torch.int64, device=dev)
+    edge_id = torch.empty(E_cap, dtype=torch.int64, device=dev)
+    new_ei = torch.empty(2, E_cap, dtype=torch.int64, device=dev)
+    new_batch = None if shares_nodes else torch.empty(N_cap, dtype=torch.int64, device=dev)
+    some = lambda t: ptr(t) if t is not None and t.numel() else None
+    call("gsat_subgraph_padded", some(ei), E, N, None if shares_nodes or not N else ptr(batch), real_graphs, some(keep), mode,
+         int(bool(drop_isolated)), ptr(valid_in) if valid_in is not None else None, num_graphs - 1, N_cap, E_cap, ptr(node_id),
+         some(edge_id), some(new_ei), some(new_batch), some(edge_mask), ptr(valid), ptr(ws), ws_bytes, stream())
+    if not (sync_free() or torch.cuda.is_current_stream_capturing()) and int(valid[3]):          # the one host read
+        raise ValueError(_overflow_text((N_cap, E_cap)))
+    sub = PaddedSubgraphBatch(x=x if shares_nodes else _take_padded(x, node_id), edge_index=new_ei,
+                              batch=batch if shares_nodes else new_batch, y=getattr(data, "y", None), num_graphs=num_graphs, valid=valid,
+                              capacity=(N_cap, E_cap), node_id=node_id, edge_id=edge_id, edge_mask=edge_mask.view(torch.bool))
+    for name, index in (("edge_attr", edge_id), ("edge_label", edge_id), ("edge_att", edge_id), ("node_label", node_id)):
+        t = getattr(data, name, None)
+        if isinstance(t, torch.Tensor):
+            _need_cuda(t)
+            if int(t.shape[0]) != (E if index is edge_id else N):
+                raise ValueError(f"{name} has {t.shape[0]} rows")
+            t = t if (index is node_id and shares_nodes) else _take_padded(t, index)
+        if t is not None or name != "edge_att":
+            setattr(sub, name, t)
+    for name in ("ragged", "r"):
+        if hasattr(data, name):
+            setattr(sub, name, getattr(data, name))
+    return sub
+
+
+def edge_subgraph_padded(data, edge_keep: torch.Tensor, capacity: Tuple[int, int], drop_isolated: bool = False) -> PaddedSubgraphBatch:
+    """:func:`edge_subgraph` into a batch of the fixed shape ``capacity = (N_cap, E_cap)`` (gsat_subgraph_padded): the kept nodes and
+    edges first, bit for bit what ``edge_subgraph`` returns, the slack as the padding graph of ``collate_padded``, the counts in
+    ``valid`` on the device.  No size is needed from the host and none is read: the call is capturable, and its result goes wherever a
+    ``PaddedBatch`` goes (``padded(sub.valid, sub.capacity)``).
+
+    ``data``: a ``Batch`` of ``G`` graphs -- the result has ``G + 1``, graph ``G`` being the padding graph -- or a ``PaddedBatch``, whose
+    ``valid`` is honoured: its padding rows and slots are never kept and ``edge_keep`` is not even read there, its own padding graph
+    stays the padding graph, ``ragged`` and ``r`` are carried over.  ``x``, ``edge_attr``, ``edge_label``, ``node_label`` and an
+    optional ``edge_att`` are gathered with zero rows in the padding; with ``drop_isolated=False`` on a ``PaddedBatch`` of ``N_cap`` rows
+    ``x``, ``batch`` and ``node_label`` are the input's own tensors (nothing decides on the host, so also when the extraction overflows:
+    see below).
+
+    An extraction that does not fit (``N' + 2 > N_cap`` or ``E' > E_cap``), whose input had overflowed or that met a bad node id is all
+    padding with ``valid == (0, 0, 0, 1)``: a ValueError after one host read of ``valid`` -- in sync-free mode or under capture
+    nothing is read and ``.check()`` reports it.  The one exception to "all padding": where ``x`` and ``batch`` are the input's own
+    tensors they stay what the input holds, real rows and graph ids included; ``valid``, ``edge_index``, ``node_id``, ``edge_id`` and the
+    gathered edge attributes are the all-padding ones, and everything that counts by ``valid`` (``padded()``, the logs) sees no row."""
+    if not isinstance(edge_keep, torch.Tensor):
+        raise ValueError("edge_keep must be a tensor")
+    return _extract_padded(data, edge_keep, 0, drop_isolated, capacity)
+
+
+def node_subgraph_padded(data, node_keep: torch.Tensor, capacity: Tuple[int, int]) -> PaddedSubgraphBatch:
+    """:func:`node_subgraph` into a batch of the fixed shape ``capacity``; see :func:`edge_subgraph_padded`.  ``node_keep``: a mask
+    [N] (an id list would need its length on the host)."""
+    if not isinstance(node_keep, torch.Tensor):
+        raise ValueError("node_keep must be a tensor")
+    if node_keep.dtype == torch.int64:
+        raise ValueError("node_subgraph_padded takes a mask, not an id list")
+    return _extract_padded(data, node_keep, 1, False, capacity)
 
 
 def explanation_subgraph(att, data, k: Optional[int] = None, ratio: Optional[float] = None, complement: bool = False,

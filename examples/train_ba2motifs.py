@@ -23,10 +23,15 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
     training-mode attention, logits and losses to a device log inside the captured graph, and each report line is followed by the
     scores of the training epoch (``epoch_scores()``: two host reads, no second pass over the training ids).
 
+  * ``--graph [--ragged] --fidelity K`` -- each report line is followed by the fidelity of the top-K explanation on the test split
+    (``dp_gsat_amd.ReplayedFidelity``): a third captured graph cuts the K best edges of every graph out on the device, runs the backbone
+    on the full batch, on the explanation alone and on the batch without it, and logs the probabilities; one host read per epoch.
+
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --train-scores
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity 5
 """
 import argparse
 import os
@@ -80,6 +85,7 @@ def main():
     ap.add_argument("--graph", action="store_true", help="train full batches as replays of one captured hipGraph (single process)")
     ap.add_argument("--ragged", action="store_true", help="with --graph: budget batches of a ragged graph count, every batch a replay")
     ap.add_argument("--train-scores", action="store_true", help="with --graph --ragged: log the training pass and print its scores")
+    ap.add_argument("--fidelity", type=int, default=None, metavar="K", help="with --graph: print the fidelity of the top-K explanation on the test split")
     args = ap.parse_args()
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -89,6 +95,8 @@ def main():
         ap.error("--ragged batches are replays: it needs --graph")
     if args.train_scores and not args.ragged:
         ap.error("--train-scores logs replays of every batch: it needs --graph --ragged")
+    if args.fidelity is not None and not args.graph:
+        ap.error("--fidelity replays a captured fidelity batch: it needs --graph")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     if world > 1:
@@ -128,7 +136,7 @@ def main():
                                  G.precision_at_k(att, b.edge_label, 5, b.batch, b.edge_index, b.num_graphs).double().mean()]).tolist()
         return acc, auc, prec
 
-    replayed = replayed_eval = None
+    replayed = replayed_eval = replayed_fidelity = None
     if args.ragged:
         # the budget of a batch: batch_size graphs of the mean size (never less than the largest graph alone); one host read
         slots = min(args.batch_size, len(graphs))
@@ -137,10 +145,14 @@ def main():
         capacity = (max(int(np.ceil(n_mean * slots)), int(n_max)) + 2, max(int(np.ceil(e_mean * slots)), int(e_max)))
         replayed = G.ReplayedStep(gsat, ds, slots, capacity=capacity, ragged=True, log_k=5 if args.train_scores else None)
         replayed_eval = G.ReplayedEval(gsat, ds, slots, 5, capacity=capacity, ragged=True)
+        if args.fidelity is not None:
+            replayed_fidelity = G.ReplayedFidelity(gsat, ds, slots, k=args.fidelity, capacity=capacity, ragged=True)
     elif args.graph and n_train >= args.batch_size:
         replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
     if args.graph and not args.ragged:
         replayed_eval = G.ReplayedEval(gsat, ds, min(args.batch_size, len(graphs)), 5)
+        if args.fidelity is not None:
+            replayed_fidelity = G.ReplayedFidelity(gsat, ds, min(args.batch_size, len(graphs)), k=args.fidelity)
 
     def evaluate_replayed(ids, epoch):
         res = replayed_eval.run(ids, epoch)      # full batches: replays; the tail: eager (--ragged: a replay too); one scoring pass at the end
@@ -181,6 +193,10 @@ def main():
             acc, auc, prec = evaluate_replayed(test_ids, epoch) if replayed_eval is not None else evaluate(test_ids)
             print(f"epoch {epoch + 1:3d}  train loss {float(tot) / nb:.4f}  test acc {acc:.3f}  attention ROC-AUC vs motif edges {auc:.3f}  prec@5 {prec:.3f}",
                   flush=True)
+            if replayed_fidelity is not None:                     # needs no edge labels: three backbone forwards per batch, one host read
+                res = replayed_fidelity.run(test_ids)
+                print(f"      fidelity@{args.fidelity}  fidelity_plus {res['fidelity_plus']:.4f}  fidelity_minus {res['fidelity_minus']:.4f}  "
+                      f"flip_plus {res['flip_plus']:.3f}  flip_minus {res['flip_minus']:.3f}", flush=True)
             if args.train_scores:                                 # scored from what the replays of this epoch logged: no eager batch
                 res = replayed.epoch_scores()
                 print(f"      train  loss {res['loss']:.4f}  pred {res['pred']:.4f}  info {res['info']:.4f}  acc {res['clf_acc']:.3f}  "

@@ -875,6 +875,32 @@ int gsat_subgraph_index(const int64_t* edge_index, int64_t num_edges, int64_t nu
                         void* stream);
 
 /*
+ * gsat_subgraph_index into outputs of a fixed CAPACITY (cap_nodes, cap_edges), independent of the input's shape: the result is a
+ * padded batch in the layout of gsat_collate_padded and no size is ever needed on the host.  mode / drop_isolated / keep, the order,
+ * the relabelling and the bad-id rule are those of gsat_subgraph_index.
+ * valid_in int32[4] (nullable): the valid word (N_real, E_real, graphs, overflow) of a padded input.  Node rows >= valid_in[0] and
+ * edge slots >= valid_in[1] are never kept, in every mode (drop_isolated == 0 keeps every REAL node), and keep is not read there; an
+ * edge slot below valid_in[1] with an endpoint outside [0, valid_in[0]) is a bad id.  pad_graph: the graph id of the padding nodes --
+ * num_graphs - 1 of a padded input, G for an unpadded input of G graphs (the result then has G + 1 graphs).
+ * Outputs: node_id int64[cap_nodes], edge_id int64[cap_edges], new_edge_index int64[2, cap_edges], new_batch int64[cap_nodes]
+ * (nullable together with batch), edge_mask uint8[E] (0 in the slots that are not counted), valid_out int32[4].
+ *   rows < N', slots < E'   what gsat_subgraph_index writes
+ *   rows >= N'              padding nodes: new_batch = pad_graph, node_id = -1
+ *   slots >= E'             padding edges, edge_id = -1, by the rule of gsat_collate_padded with N = N', E = E', n_pad = cap_nodes - N',
+ *                           e_pad = cap_edges - E' (one __device__ function serves both kernels)
+ *   valid_out               (N', E', g, 0) with g = valid_in[2], or G without valid_in
+ * Overflow -- N' + 2 > cap_nodes, E' > cap_edges, valid_in[3] != 0 or a bad id: valid_out = (0, 0, 0, 1) and every row and slot is
+ * padding.  Nothing is ever written out of bounds.
+ * Launches: 5 (7 in edge mode with drop_isolated), independent of G, N, E; kernels only, no memset / memcpy nodes, nothing read back
+ * (capturable).  N, E, G, the capacities < 2^31 (GSAT_ERR_UNSUPPORTED otherwise); cap_nodes >= 2.
+ * workspace: gsat_subgraph_workspace_bytes(N, E).
+ */
+int gsat_subgraph_padded(const int64_t* edge_index, int64_t num_edges, int64_t num_nodes, const int64_t* batch, int64_t num_graphs,
+                         const uint8_t* keep, int mode, int drop_isolated, const int32_t* valid_in, int64_t pad_graph, int64_t cap_nodes,
+                         int64_t cap_edges, int64_t* node_id, int64_t* edge_id, int64_t* new_edge_index, int64_t* new_batch,
+                         uint8_t* edge_mask, int32_t* valid_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * out[i,:] = table[index[i],:] for n rows of row_bytes >= 1 bytes each, any dtype (both row-major, contiguous).  16-byte lanes when
  * row_bytes, table and out are all 16-byte aligned, otherwise 8-, 4- or 1-byte lanes from the actual alignment.  The indices are
  * trusted (they come from gsat_subgraph_index).
@@ -924,6 +950,38 @@ int64_t gsat_delta_kl_segments_chunk(void);
 size_t gsat_delta_kl_segments_workspace_bytes(int64_t num_segments, int64_t max_seg_len);
 int gsat_delta_kl_segments(const float* att, const uint8_t* label, const int64_t* seg_ptr, int64_t num_segments, int64_t num_edges,
                            int64_t max_seg_len, double eps, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ================================= explanation fidelity log ================================= */
+
+/*
+ * Appends one batch to a device-resident log of explanation fidelity, at the offset held in log_state int64[4] = (graphs logged,
+ * batches logged, flags, 0) ON THE DEVICE; two launches (the rows, then one thread that advances log_state), nothing read back, launch
+ * geometry from graph_rows only (capturable, kernels only).
+ * logits_full / logits_keep / logits_drop fp32[graph_rows, classes], classes >= 1: the backbone on the full graph, on the explanation
+ * alone and on the graph without the explanation.  valid int32[4] (nullable) = (N_real, E_real, B, overflow) of a padded batch: with it
+ * g = clamp(valid[2], 0, graph_rows) rows are logged, without it all graph_rows; rows >= g are never loaded.
+ * Per graph i < g, at slot g0 + i:
+ *   log_cls int32[max_graphs, 3]   the classes predicted from the three blocks
+ *   log_p  double[max_graphs, 3]   the probability, under each block, of the class predicted from logits_full
+ * classes == 1: class = (z >= 0), p = sigmoid(+z) for class 1 and sigmoid(-z) for class 0.  classes > 1: argmax with the lowest index on
+ * ties, softmax with the row maximum subtracted, evaluated in fp64 from the fp32 logits.  NaN logits are unsupported.
+ * A batch whose valid[3] is set appends nothing and sets flag bit 0; a batch that would exceed max_graphs appends nothing and sets flag
+ * bit 1.  max_graphs, graph_rows < 2^31 (GSAT_ERR_UNSUPPORTED otherwise).
+ * replaces: nothing in the reference -- the host loop of example/trainer.py:140-170 stops at the extracted subgraph.
+ */
+int gsat_fidelity_append(const float* logits_full, const float* logits_keep, const float* logits_drop, int64_t graph_rows, int64_t classes,
+                         const int32_t* valid, int32_t* log_cls, double* log_p, int64_t* log_state, int64_t max_graphs, void* stream);
+
+/*
+ * One launch of one workgroup: out int64[10] = (graphs, batches, flags, #(cls_drop != cls_full), #(cls_keep != cls_full)) and the bit
+ * patterns of five doubles -- the sums over the logged graphs of p_full - p_drop, p_full - p_keep, p_full, p_keep, p_drop.  fp64 sums in
+ * a fixed order, no float atomics: bitwise repeatable.  The caller reads out once and divides by the count.
+ */
+int gsat_fidelity_reduce(const int32_t* log_cls, const double* log_p, const int64_t* log_state, int64_t max_graphs, int64_t* out,
+                         void* stream);
+
+/* log_state = (0, 0, 0, 0), by a kernel (no memset node). */
+int gsat_fidelity_reset(int64_t* log_state, void* stream);
 
 #ifdef __cplusplus
 }
