@@ -14,16 +14,18 @@ from .gsat import (GSAT, ExtractorMLP, concrete_sample, get_r, gumbel_sigmoid, i
                    lift_node_att_to_edge_att, symmetrise_edge_att)
 from .collate import PackedDataset, PaddedBatch, collate_padded_pair, line_graph, line_graph_undirected
 from .padding import current_padding, padded
-from .replay import ReplayedDualEval, ReplayedDualStep, ReplayedEval, ReplayedFidelity, ReplayedStep
+from .replay import ReplayedDualEval, ReplayedDualStep, ReplayedEval, ReplayedFidelity, ReplayedFidelityCurve, ReplayedStep
 from .dual_gsat import DualGSAT, f1_sparsity_loss, f1_sparsity_loss_valid
 from .graph_index import BatchIndex, clear_cache, get_index, set_strict, set_sync_free
 from .utils import process_data, reorder_like, set_seed
 from .explain import EdgeRanking, ExplanationMeter, attention_auroc, delta_kl, precision_at_k, rank_edges, topk_edge_mask
+from .explain import explanation_levels
 from .subgraph import (PaddedSubgraphBatch, SubgraphBatch, edge_subgraph, edge_subgraph_padded, explanation_fidelity, explanation_subgraph,
                        gather_rows, node_subgraph, node_subgraph_padded)
+from .subgraph import StackedExplanationBatch, explanation_fidelity_curve, explanation_stack
 from .evaluate import (AttentionHistogram, EvaluationMeter, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve,
                        task_auroc_counts)
-from .eval_log import EpochLog, FidelityLog, delta_kl_segments
+from .eval_log import EpochLog, FidelityCurveLog, FidelityLog, delta_kl_segments
 
 __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "get_preds", "GINConv", "GINEConv",
            "PNAConvSimple", "GIN", "PNA", "GSAT", "ExtractorMLP", "concrete_sample", "get_r", "gumbel_sigmoid",
@@ -34,4 +36,6 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "AttentionHistogram", "EvaluationMeter", "attention_histogram", "classifier_accuracy", "classifier_rocauc", "pr_curve",
            "task_auroc_counts", "PaddedBatch", "padded", "current_padding", "ReplayedStep",
            "ReplayedDualStep", "collate_padded_pair", "f1_sparsity_loss_valid", "EpochLog", "delta_kl_segments", "ReplayedEval",
-           "ReplayedDualEval", "criterion_valid", "PaddedSubgraphBatch", "edge_subgraph_padded", "node_subgraph_padded", "FidelityLog", "ReplayedFidelity"]
+           "ReplayedDualEval", "criterion_valid", "PaddedSubgraphBatch", "edge_subgraph_padded", "node_subgraph_padded", "FidelityLog", "ReplayedFidelity",
+           "explanation_levels", "StackedExplanationBatch", "explanation_stack", "explanation_fidelity_curve", "FidelityCurveLog",
+           "ReplayedFidelityCurve"]

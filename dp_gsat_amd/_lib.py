@@ -137,6 +137,13 @@ SIGNATURES = {
     "gsat_fidelity_append": (INT, [P, P, P, I64, I64, P, P, P, P, I64, P]),
     "gsat_fidelity_reduce": (INT, [P, P, P, I64, P, P]),
     "gsat_fidelity_reset": (INT, [P, P]),
+    "gsat_fidelity_levels": (INT, [P, P, P, I64, I64, P, P, I64, P, P]),
+    "gsat_fidelity_stack_block_items": (I64, []),
+    "gsat_fidelity_stack_workspace_bytes": (SZ, [I64, I64]),
+    "gsat_fidelity_stack": (INT, [P, I64, I64, P, I64, P, P, I64, I64, I64, P, P, P, P, P, P, SZ, P]),
+    "gsat_fidelity_curve_append": (INT, [P, I64, I64, I64, P, P, P, P, P, I64, P]),
+    "gsat_fidelity_curve_reduce": (INT, [P, P, P, I64, I64, P, P]),
+    "gsat_fidelity_curve_reset": (INT, [P, P]),
 }
 
 

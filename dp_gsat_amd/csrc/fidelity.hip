@@ -7,6 +7,7 @@
 //   gsat_fidelity_reduce : the sums of everything logged, by one workgroup in a fixed order (fp64, no float atomics: bitwise
 //                          repeatable), packed with the counters for ONE host read.
 //   gsat_fidelity_reset  : zeroes the counters with a kernel (no memset node).
+//   gsat_fidelity_curve_append / _reduce / _reset : the same log with a level axis, for the logits of a stacked batch (fidelity_stack.hip).
 #include "common.h"
 #include <algorithm>
 
@@ -126,6 +127,98 @@ k_fid_reduce(const int32_t* __restrict__ log_cls, const double* __restrict__ log
     }
 }
 
+// ---- the level-aware log of a fidelity curve (dp_gsat_amd/eval_log.py: FidelityCurveLog) ---------------------------------------------------
+// One batch is the logits of a stacked batch (fidelity_stack.hip): V = 2 S + 1 blocks of Gp rows -- the full batch, level s alone, the batch
+// without level s.  state int64[FIDC_STATE] = (graphs, batches, flags, real edges, kept edges of level 0 .. 15).
+constexpr int FIDC_MAX_LEVELS = 16;
+constexpr int FIDC_STATE = 4 + FIDC_MAX_LEVELS;
+
+// fid_plan for a stacked batch: the graph count is the input's valid[2] (without it the full variant's), and the batch is refused when
+// the input or any variant of the stack had overflowed
+__device__ __forceinline__ FidPlan fidc_plan(const int32_t* __restrict__ valid, const int32_t* __restrict__ stack_valid, int V, int64_t Gp,
+                                             const int64_t* __restrict__ state, int64_t max_graphs) {
+    FidPlan p;
+    p.g0 = state[0];
+    p.g = 0;
+    p.flag = 0;
+    int over = valid != nullptr && valid[3] != 0;
+    for (int v = 0; v < V; ++v) over |= stack_valid[4 * v + 3] != 0;
+    if (over) { p.flag = FID_FLAG_OVERFLOW; return p; }
+    const int64_t g = min<int64_t>(max<int64_t>(valid != nullptr ? valid[2] : stack_valid[2], 0), Gp);
+    if (p.g0 < 0 || p.g0 + g > max_graphs) { p.flag = FID_FLAG_FULL; return p; }
+    p.g = g;
+    return p;
+}
+
+// one thread per (graph, variant) below the count: the variant's class, and its probability of the class predicted from the full variant
+__global__ void __launch_bounds__(FID_BLOCK)
+k_fidc_rows(const float* __restrict__ logits, int64_t Gp, int C, int V, const int32_t* __restrict__ valid, const int32_t* __restrict__ stack_valid,
+            int32_t* __restrict__ log_cls, double* __restrict__ log_p, const int64_t* __restrict__ state, int64_t max_graphs) {
+    const FidPlan p = fidc_plan(valid, stack_valid, V, Gp, state, max_graphs);
+    if (p.flag) return;
+    const int64_t stride = (int64_t)gridDim.x * FID_BLOCK, items = p.g * V;
+    for (int64_t t = (int64_t)blockIdx.x * FID_BLOCK + threadIdx.x; t < items; t += stride) {
+        const int64_t i = t / V, v = t - i * V;
+        const float *zf = logits + i * C, *zv = logits + (v * Gp + i) * C;
+        const int cls = fid_class(zf, C);
+        log_cls[(p.g0 + i) * V + v] = v == 0 ? cls : fid_class(zv, C);
+        log_p[(p.g0 + i) * V + v] = fid_prob(zv, C, cls);
+    }
+}
+
+__global__ void k_fidc_commit(int64_t Gp, int V, const int32_t* __restrict__ valid, const int32_t* __restrict__ stack_valid,
+                              int64_t* __restrict__ state, int64_t max_graphs) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const FidPlan p = fidc_plan(valid, stack_valid, V, Gp, state, max_graphs);
+    if (p.flag) { state[2] |= (int64_t)p.flag; return; }
+    state[0] = p.g0 + p.g;
+    state[1] += 1;
+    state[3] += stack_valid[1];
+    for (int s = 0; s < (V - 1) / 2; ++s) state[4 + s] += stack_valid[4 * (1 + s) + 1];
+}
+
+__global__ void k_fidc_reset(int64_t* __restrict__ state) {
+    if (blockIdx.x == 0 && threadIdx.x < FIDC_STATE) state[threadIdx.x] = 0;
+}
+
+// out int64[5 + 7 S]: (graphs, batches, flags, real edges), kept edges [S], #(cls_drop_s != cls_full) [S], #(cls_keep_s != cls_full) [S],
+// then the bits of doubles: the sum of p_full, and per level the sums of p_keep, p_drop, p_full - p_drop, p_full - p_keep ([S] each).
+// One workgroup; thread t adds rows t, t + 256, ... in that order, level after level.
+__global__ void __launch_bounds__(FID_BLOCK)
+k_fidc_reduce(const int32_t* __restrict__ log_cls, const double* __restrict__ log_p, const int64_t* __restrict__ state, int64_t max_graphs, int S,
+              int64_t* __restrict__ out) {
+    __shared__ double sh[FID_BLOCK / 64];
+    const int V = 2 * S + 1;
+    const int64_t n = min<int64_t>(max<int64_t>(state[0], 0), max_graphs);
+    double full = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += FID_BLOCK) full += log_p[i * V];
+    full = fid_block_sum(full, sh);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 4; ++k) out[k] = state[k];
+        for (int s = 0; s < S; ++s) out[4 + s] = state[4 + s];
+        out[4 + 3 * S] = __double_as_longlong(full);
+    }
+    for (int s = 0; s < S; ++s) {
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, flips[2] = {0.0, 0.0};          // counts below 2^31: exact in fp64
+        for (int64_t i = threadIdx.x; i < n; i += FID_BLOCK) {
+            const int32_t* c = log_cls + i * V;
+            const double* p = log_p + i * V;
+            const double pk = p[1 + s], pd = p[1 + S + s];
+            a[0] += pk; a[1] += pd; a[2] += p[0] - pd; a[3] += p[0] - pk;
+            flips[0] += c[1 + S + s] != c[0] ? 1.0 : 0.0;
+            flips[1] += c[1 + s] != c[0] ? 1.0 : 0.0;
+        }
+        double t[6];
+        for (int k = 0; k < 4; ++k) t[k] = fid_block_sum(a[k], sh);
+        for (int k = 0; k < 2; ++k) t[4 + k] = fid_block_sum(flips[k], sh);
+        if (threadIdx.x == 0) {
+            out[4 + S + s] = (int64_t)t[4];
+            out[4 + 2 * S + s] = (int64_t)t[5];
+            for (int k = 0; k < 4; ++k) out[5 + (3 + k) * S + s] = __double_as_longlong(t[k]);
+        }
+    }
+}
+
 }  // namespace gsat
 
 using namespace gsat;
@@ -163,6 +256,44 @@ int gsat_fidelity_reset(int64_t* log_state, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     GSAT_REQUIRE(log_state, GSAT_ERR_ARG, "gsat_fidelity_reset: null pointer");
     k_fid_reset<<<1, 64, 0, stream>>>(log_state);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_fidelity_curve_append(const float* logits, int64_t graphs_per_variant, int64_t classes, int64_t levels, const int32_t* valid,
+                               const int32_t* stack_valid, int32_t* log_cls, double* log_p, int64_t* log_state, int64_t max_graphs,
+                               void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(graphs_per_variant >= 0 && classes >= 1 && max_graphs >= 0 && levels >= 1 && levels <= FIDC_MAX_LEVELS, GSAT_ERR_ARG,
+                 "gsat_fidelity_curve_append: bad extent (1..16 levels)");
+    const int V = 2 * (int)levels + 1;
+    GSAT_REQUIRE(graphs_per_variant < (1ll << 31) / V && classes < (1ll << 31) && max_graphs < (1ll << 31) / V, GSAT_ERR_UNSUPPORTED,
+                 "gsat_fidelity_curve_append: >2^31 entries");
+    GSAT_REQUIRE(log_state && stack_valid && (graphs_per_variant == 0 || logits) && (max_graphs == 0 || (log_cls && log_p)), GSAT_ERR_ARG,
+                 "gsat_fidelity_curve_append: null pointer");
+    const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(graphs_per_variant * V, FID_BLOCK), 1), FID_MAX_BLOCKS);
+    k_fidc_rows<<<blocks, FID_BLOCK, 0, stream>>>(logits, graphs_per_variant, (int)classes, V, valid, stack_valid, log_cls, log_p, log_state,
+                                                  max_graphs);
+    GSAT_LAUNCH_CHECK();
+    k_fidc_commit<<<1, 64, 0, stream>>>(graphs_per_variant, V, valid, stack_valid, log_state, max_graphs);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_fidelity_curve_reduce(const int32_t* log_cls, const double* log_p, const int64_t* log_state, int64_t max_graphs, int64_t levels,
+                               int64_t* out, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(max_graphs >= 0 && levels >= 1 && levels <= FIDC_MAX_LEVELS && log_state && out && (max_graphs == 0 || (log_cls && log_p)),
+                 GSAT_ERR_ARG, "gsat_fidelity_curve_reduce: bad argument");
+    k_fidc_reduce<<<1, FID_BLOCK, 0, stream>>>(log_cls, log_p, log_state, max_graphs, (int)levels, out);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_fidelity_curve_reset(int64_t* log_state, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(log_state, GSAT_ERR_ARG, "gsat_fidelity_curve_reset: null pointer");
+    k_fidc_reset<<<1, 64, 0, stream>>>(log_state);
     GSAT_LAUNCH_CHECK();
     return GSAT_OK;
 }

@@ -18,6 +18,7 @@
 // input from its valid word, the scan writes valid_out = (N', E', graphs, overflow), the two output passes emit the real part and one
 // more pass (k_subp_fill) turns the slack into the padding graph by the rule of gsat_collate_padded.  5 launches (7), no size read back.
 #include "common.h"
+#include "compact.h"
 #include <algorithm>
 
 namespace gsat {
@@ -76,32 +77,6 @@ __device__ __forceinline__ void load_ids8(const int64_t* __restrict__ p, int64_t
     }
 }
 
-// Rank of this thread's first item among the workgroup's flagged items (items in thread order, SUB_IPT per thread), and the
-// workgroup's total.  One ballot per item slot: the flagged items of the lanes below come out of popcounts of the masked ballots.
-__device__ __forceinline__ int block_rank(uint32_t bits, int* sh, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t below = (1ull << lane) - 1ull;
-    int before = 0, wave_total = 0;
-#pragma unroll
-    for (int j = 0; j < SUB_IPT; ++j) {
-        const uint64_t m = __ballot((bits >> j) & 1u);
-        before += __popcll(m & below);
-        wave_total += __popcll(m);
-    }
-    __syncthreads();
-    if (lane == 0) sh[wave] = wave_total;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < SUB_BLOCK / 64; ++w) {
-        const int c = sh[w];
-        if (w < wave) base += c;
-        total += c;
-    }
-    return base + before;
-}
-
 __global__ void __launch_bounds__(SUB_BLOCK) k_sub_clear(uint4* __restrict__ p, int64_t n16) {
     const int64_t i = (int64_t)blockIdx.x * SUB_BLOCK + threadIdx.x;
     if (i < n16) p[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -129,7 +104,7 @@ __device__ __forceinline__ void sub_flags(const int64_t* __restrict__ ei, int64_
             bits = left >= SUB_IPT ? 0xFFu : (left > 0 ? (1u << left) - 1u : 0u);
         }
         if (node_src != node_flag) store_flags8(node_flag, i0, N, bits);
-        (void)block_rank(bits, sh, total);
+        (void)block_rank<SUB_IPT, SUB_BLOCK>(bits, sh, total);
         if (threadIdx.x == 0) cnt_n[blockIdx.x] = total;
         return;
     }
@@ -154,7 +129,7 @@ __device__ __forceinline__ void sub_flags(const int64_t* __restrict__ ei, int64_
         }
     }
     store_flags8(edge_mask, i0, E, bits);
-    (void)block_rank(bits, sh, total);
+    (void)block_rank<SUB_IPT, SUB_BLOCK>(bits, sh, total);
     any_bad = __syncthreads_or(any_bad);
     if (threadIdx.x == 0) { cnt_e[b] = total; bad[b] = any_bad ? 1 : 0; }
 }
@@ -188,42 +163,13 @@ k_subp_flags(const int64_t* __restrict__ ei, int64_t E, int64_t N, const int32_t
     sub_flags(ei, E, N, Ev, Nv, edge_keep, node_keep, node_src, node_flag, mark, nb_nodes, edge_mask, cnt_n, cnt_e, bad, sh);
 }
 
-// exclusive scan of a[0 .. n) in place by the one workgroup; returns the total in every thread
-__device__ __forceinline__ int scan_counts(int32_t* __restrict__ a, int n, int* sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < n; base += SUB_SCAN_BLOCK) {
-        const int i = base + (int)threadIdx.x;
-        const int v = i < n ? a[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) sh[wave] = incl;
-        __syncthreads();
-        int wave_base = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < SUB_SCAN_BLOCK / 64; ++w) {
-            const int c = sh[w];
-            if (w < wave) wave_base += c;
-            tot += c;
-        }
-        if (i < n) a[i] = carry + wave_base + incl - v;
-        carry += tot;
-        __syncthreads();
-    }
-    return carry;
-}
-
 // second scan level: workgroup counts -> workgroup offsets (the totals behind them), and counts = (N', E', overflow, bad id)
 __global__ void __launch_bounds__(SUB_SCAN_BLOCK)
 k_sub_scan(int32_t* __restrict__ cnt_n, int nb_nodes, int32_t* __restrict__ cnt_e, int nb_edges, const int32_t* __restrict__ bad,
            int64_t cap_nodes, int64_t cap_edges, int exact, int64_t* __restrict__ counts) {
     __shared__ int sh[SUB_SCAN_BLOCK / 64];
-    const int kept_n = scan_counts(cnt_n, nb_nodes, sh);
-    const int kept_e = scan_counts(cnt_e, nb_edges, sh);
+    const int kept_n = scan_counts<SUB_SCAN_BLOCK>(cnt_n, nb_nodes, sh);
+    const int kept_e = scan_counts<SUB_SCAN_BLOCK>(cnt_e, nb_edges, sh);
     int any_bad = 0;
     for (int i = threadIdx.x; i < nb_edges; i += SUB_SCAN_BLOCK) any_bad |= bad[i];
     any_bad = __syncthreads_or(any_bad);
@@ -250,7 +196,7 @@ k_sub_node_out(const uint8_t* __restrict__ node_flag, int64_t N, const int32_t* 
     const int64_t i0 = (int64_t)b * SUB_ITEMS + (int64_t)threadIdx.x * SUB_IPT;
     const uint32_t bits = b < nb_nodes ? load_flags8(node_flag, i0, N) : 0u;
     int total;
-    const int first = off_n[b < nb_nodes ? b : nb_nodes] + block_rank(bits, sh, total);
+    const int first = off_n[b < nb_nodes ? b : nb_nodes] + block_rank<SUB_IPT, SUB_BLOCK>(bits, sh, total);
     int r[SUB_IPT];
 #pragma unroll
     for (int j = 0; j < SUB_IPT; ++j) r[j] = first + __popc(bits & ((1u << j) - 1u));
@@ -299,7 +245,7 @@ k_sub_edge_out(const int64_t* __restrict__ ei, int64_t E, int64_t N, const uint8
     const int64_t i0 = (int64_t)b * SUB_ITEMS + (int64_t)threadIdx.x * SUB_IPT;
     const uint32_t bits = load_flags8(edge_mask, i0, E);
     int total;
-    const int first = off_e[b] + block_rank(bits, sh, total);
+    const int first = off_e[b] + block_rank<SUB_IPT, SUB_BLOCK>(bits, sh, total);
     int64_t s[SUB_IPT], d[SUB_IPT];
     load_ids8(ei, i0, E, s);
     load_ids8(ei + E, i0, E, d);
@@ -326,8 +272,8 @@ __global__ void __launch_bounds__(SUB_SCAN_BLOCK)
 k_subp_scan(int32_t* __restrict__ cnt_n, int nb_nodes, int32_t* __restrict__ cnt_e, int nb_edges, const int32_t* __restrict__ bad,
             int64_t cap_nodes, int64_t cap_edges, const int32_t* __restrict__ valid_in, int64_t G, int32_t* __restrict__ valid_out) {
     __shared__ int sh[SUB_SCAN_BLOCK / 64];
-    const int kept_n = scan_counts(cnt_n, nb_nodes, sh);
-    const int kept_e = scan_counts(cnt_e, nb_edges, sh);
+    const int kept_n = scan_counts<SUB_SCAN_BLOCK>(cnt_n, nb_nodes, sh);
+    const int kept_e = scan_counts<SUB_SCAN_BLOCK>(cnt_e, nb_edges, sh);
     int any_bad = 0;
     for (int i = threadIdx.x; i < nb_edges; i += SUB_SCAN_BLOCK) any_bad |= bad[i];
     any_bad = __syncthreads_or(any_bad);

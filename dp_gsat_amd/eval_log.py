@@ -23,7 +23,7 @@ import torch
 
 from ._lib import GsatHipError, call, ptr, stream
 from .evaluate import MAX_BINS, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve
-from .explain import _att, _labels, attention_auroc, delta_kl_stats, rank_edges_lds_cap
+from .explain import _att, _labels, attention_auroc, check_levels, delta_kl_stats, rank_edges_lds_cap
 from .graph_index import call_size, get_index
 
 FLAG_OVERFLOW, FLAG_FULL = 1, 2
@@ -267,3 +267,80 @@ class FidelityLog:
         return {"fidelity_plus": float(sums[0]) / n, "fidelity_minus": float(sums[1]) / n, "p_full": float(sums[2]) / n,
                 "p_keep": float(sums[3]) / n, "p_drop": float(sums[4]) / n, "flip_plus": flips_plus / n, "flip_minus": flips_minus / n,
                 "n": n}
+
+
+class FidelityCurveLog:
+    """``FidelityCurveLog(max_graphs, classes, ks=None, ratios=None, device=None)``: :class:`FidelityLog` with a level axis, for the
+    logits of a stacked batch (``dp_gsat_amd.subgraph.explanation_stack``: ``V = 2 S + 1`` blocks -- the batch, level s alone, the batch
+    without level s).  ``append`` keeps, per graph, the class predicted from every block (``cls int32[max_graphs, V]``) and every block's
+    probability of the class predicted from the full batch (``p float64[max_graphs, V]``); ``state`` int64[20] = (graphs, batches, flags,
+    real edges, kept edges of level 0 .. 15) lives on the device.  ``append`` is two kernel launches and reads nothing, so it replays inside
+    a captured graph (``ReplayedFidelityCurve``).  An append that cannot be taken -- an overflowed batch or stack (flag bit 0), or one that
+    would exceed ``max_graphs`` (flag bit 1) -- writes nothing but its flag and is reported by ``compute``."""
+
+    def __init__(self, max_graphs: int, classes: int, ks=None, ratios=None, device=None):
+        ks, ratios = check_levels(ks, ratios)
+        self.levels, self.by_ratio = tuple(ks if ks is not None else ratios), ratios is not None
+        S = len(self.levels)
+        self.variants = 2 * S + 1
+        if int(max_graphs) < 0 or int(classes) < 1:
+            raise ValueError("FidelityCurveLog needs a non-negative capacity and at least one logit column")
+        if int(max_graphs) * self.variants >= 2 ** 31:
+            raise ValueError("FidelityCurveLog: max_graphs * variants must be below 2**31")
+        self.max_graphs, self.classes = int(max_graphs), int(classes)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise GsatHipError("dp_gsat_amd.eval_log needs a ROCm (cuda) device: the HIP path has no CPU fallback")
+        self.cls = torch.empty((self.max_graphs, self.variants), dtype=torch.int32, device=dev)
+        self.p = torch.empty((self.max_graphs, self.variants), dtype=torch.float64, device=dev)
+        self.state = torch.zeros(20, dtype=torch.int64, device=dev)
+        self._out = torch.empty(5 + 7 * S, dtype=torch.int64, device=dev)
+
+    def reset(self) -> None:
+        """Empty the log: one kernel zeroes ``state`` (no memset node, so a captured graph may hold it), nothing is read."""
+        call("gsat_fidelity_curve_reset", ptr(self.state), stream())
+
+    def append(self, logits, stack_valid, valid=None) -> None:
+        """Log one stacked batch: ``logits`` fp32 ``[V * graphs_per_variant, classes]``, ``stack_valid`` the stack's int32[V, 4].
+        ``valid``: the int32[4] word of the padded batch the stack was made of -- ``clamp(valid[2], 0, graphs_per_variant)`` graphs are
+        logged; without it ``stack_valid[0, 2]``.  Rows of other graphs are never loaded."""
+        if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+            raise GsatHipError("dp_gsat_amd.eval_log needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+        if logits.dim() != 2 or int(logits.shape[1]) != self.classes or int(logits.shape[0]) % self.variants:
+            raise ValueError(f"logits must have shape [{self.variants} * graphs_per_variant, {self.classes}]")
+        z = logits.detach().to(torch.float32).contiguous()
+        words = [stack_valid] + ([valid] if valid is not None else [])
+        for t, n in zip(words, (4 * self.variants, 4)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() < n or not t.is_cuda:
+                raise ValueError("valid words must be int32 ROCm tensors: (N_real, E_real, B, overflow), one row per variant for the stack")
+        call("gsat_fidelity_curve_append", ptr(z) if z.numel() else None, int(z.shape[0]) // self.variants, self.classes, len(self.levels),
+             ptr(valid.contiguous()) if valid is not None else None, ptr(stack_valid.contiguous()), ptr(self.cls) if self.cls.numel() else None,
+             ptr(self.p) if self.p.numel() else None, ptr(self.state), self.max_graphs, stream())
+
+    def compute(self) -> dict:
+        """Score everything logged since ``reset``, with ONE reduction launch and ONE host read.  ``levels`` (the ``ks`` or ``ratios``);
+        per level, as lists: ``fidelity_plus = mean(p_full - p_drop)``, ``fidelity_minus = mean(p_full - p_keep)``, ``p_keep``, ``p_drop``,
+        the exact flip rates ``flip_plus = #(cls_drop != cls_full) / n`` and ``flip_minus = #(cls_keep != cls_full) / n`` and
+        ``kept_fraction`` = kept edges / real edges (integer sums); ``p_full`` and ``n``.  fp64 sums in a fixed order: two runs over the same
+        log are bitwise equal.  ValueError when an append was refused, or nothing was appended."""
+        S = len(self.levels)
+        call("gsat_fidelity_curve_reduce", ptr(self.cls) if self.cls.numel() else None, ptr(self.p) if self.p.numel() else None,
+             ptr(self.state), self.max_graphs, S, ptr(self._out), stream())
+        packed = self._out.cpu().numpy()                                                        # the one host read
+        n, batches, flags, real_edges = (int(v) for v in packed[:4])
+        if flags & FLAG_OVERFLOW:
+            raise ValueError("FidelityCurveLog: flag bit 0 is set -- a padded batch or a variant of its stack did not fit its capacity "
+                             "(valid[3]) and was not logged")
+        if flags & FLAG_FULL:
+            raise ValueError(f"FidelityCurveLog: flag bit 1 is set -- an append would have exceeded max_graphs ({self.max_graphs}) and "
+                             "was not logged")
+        if batches == 0 or n == 0:
+            raise ValueError("FidelityCurveLog.compute() before any append()")
+        ints = packed[4:4 + 3 * S].reshape(3, S)
+        sums = packed[4 + 3 * S:].view(np.float64)
+        per_level = sums[1:].reshape(4, S)
+        return {"levels": list(self.levels),
+                "fidelity_plus": [float(v) / n for v in per_level[2]], "fidelity_minus": [float(v) / n for v in per_level[3]],
+                "p_full": float(sums[0]) / n, "p_keep": [float(v) / n for v in per_level[0]], "p_drop": [float(v) / n for v in per_level[1]],
+                "flip_plus": [int(v) / n for v in ints[1]], "flip_minus": [int(v) / n for v in ints[2]],
+                "kept_fraction": [int(v) / real_edges if real_edges else 0.0 for v in ints[0]], "n": n}

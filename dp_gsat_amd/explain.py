@@ -12,6 +12,7 @@ where the symmetrised mask gives an edge and its reverse the same value.  NaN at
 """
 from __future__ import annotations
 
+import ctypes
 from typing import NamedTuple, Optional
 
 import torch
@@ -142,6 +143,50 @@ def topk_edge_mask(att, edge_index, batch, k: Optional[int] = None, ratio: Optio
     eptr, _, eg, _ = seg.edge_segments
     keep = torch.ceil((eptr[1:] - eptr[:-1]).double() * float(ratio)).to(torch.int32)
     return out["rank"] < keep[eg]
+
+
+MAX_LEVELS = 16
+
+
+def check_levels(ks=None, ratios=None):
+    """The sparsity levels of a fidelity curve as ``(ks, ratios)``, one of them a list and the other None.  ValueError unless exactly one
+    is given, with 1 to ``MAX_LEVELS`` strictly increasing entries: positive ints, or floats in (0, 1]."""
+    if (ks is None) == (ratios is None):
+        raise ValueError("give exactly one of ks and ratios")
+    levels = list(ks if ks is not None else ratios)
+    if not 1 <= len(levels) <= MAX_LEVELS:
+        raise ValueError(f"a fidelity curve takes 1 to {MAX_LEVELS} levels, got {len(levels)}")
+    if ks is not None:
+        if any(isinstance(k, bool) or int(k) != k or int(k) < 1 for k in levels):
+            raise ValueError("ks must be positive ints")
+        levels = [int(k) for k in levels]
+    else:
+        if any(not 0.0 < float(r) <= 1.0 for r in levels):
+            raise ValueError("ratios must lie in (0, 1]")
+        levels = [float(r) for r in levels]
+    if any(b <= a for a, b in zip(levels, levels[1:])):
+        raise ValueError("the levels must be strictly increasing")
+    return (levels, None) if ks is not None else (None, levels)
+
+
+def explanation_levels(att, edge_index, batch, ks=None, ratios=None, num_graphs: Optional[int] = None, *,
+                       max_seg_edges: Optional[int] = None, ranked_graphs: Optional[int] = None) -> torch.Tensor:
+    """uint8[E]: for every edge the smallest level ``s`` whose top-``ks[s]`` (or top-``ceil(ratios[s] * E_g)``) of its graph holds it,
+    ``len(levels)`` when none does -- all levels of a fidelity curve from ONE ranking, since their kept sets are nested:
+    ``explanation_levels(...) <= s`` is bit for bit ``topk_edge_mask(..., k=ks[s] | ratio=ratios[s])``.  ``ks`` / ``ratios``: exactly
+    one, 1 to 16 strictly increasing entries.  ``max_seg_edges`` / ``ranked_graphs`` as in :func:`topk_edge_mask`; an edge of a graph that
+    is not ranked gets ``len(levels)``.  Two launches (the ranking and gsat_fidelity_levels), capturable with ``max_seg_edges``."""
+    ks, ratios = check_levels(ks, ratios)
+    S = len(ks if ks is not None else ratios)
+    out, seg = _rank(att, edge_index, batch, num_graphs, "auto", want=("rank",), max_seg_edges=max_seg_edges, ranked_graphs=ranked_graphs)
+    eptr, _, _, eg32 = seg.edge_segments
+    E = seg.index.E
+    level = torch.empty(E, dtype=torch.uint8, device=out["rank"].device)
+    host_ks = (ctypes.c_int64 * S)(*ks) if ks is not None else None
+    host_ratios = (ctypes.c_double * S)(*ratios) if ratios is not None else None
+    call("gsat_fidelity_levels", ptr(out["rank"]) if E else None, ptr(eptr), ptr(eg32) if E else None, E,
+         seg.G if ranked_graphs is None else int(ranked_graphs), host_ks, host_ratios, S, ptr(level) if E else None, stream())
+    return level
 
 
 def precision_at_k(att, exp_labels, k: int, batch, edge_index, num_graphs: Optional[int] = None, path: str = "auto") -> torch.Tensor:

@@ -18,13 +18,13 @@ import torch
 from . import explain as _explain
 from ._lib import call, ptr, stream
 from .collate import collate_padded_pair
-from .eval_log import EpochLog, FidelityLog
+from .eval_log import EpochLog, FidelityCurveLog, FidelityLog
 from .evaluate import MAX_BINS
 from .graph_index import clear_cache, get_index, set_sync_free, sync_free
 from .gsat import get_r
 from .ops import edge_tensor
 from .padding import padded
-from .subgraph import edge_subgraph_padded
+from .subgraph import edge_subgraph_padded, explanation_stack
 
 _MULTI_LABEL = "a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)"
 
@@ -877,4 +877,97 @@ class ReplayedFidelity(_Replayed):
     def overflowed(self) -> bool:
         """True if a batch or an extraction since the last call (or since capture) did not fit its capacity.  One host read; clears the
         flag."""
+        return _take_overflow(self)
+
+
+class ReplayedFidelityCurve(_Replayed):
+    """``ReplayedFidelityCurve(gsat, dataset, batch_size, ks=None, ratios=None, capacity=None, max_graphs=None, graph=None,
+    ragged=False)``: the fidelity of the explanation at ``S`` sparsity levels at once -- a curve over ``ks`` (top-k per graph) or ``ratios``
+    (top-ratio), 1 to 16 strictly increasing values -- as replays of ONE captured hipGraph.  Where ``S`` ``ReplayedFidelity`` instances
+    repeat the collation, the attention, the ranking and the full-graph forward and run ``2 S`` extractions and backbone forwards, a replay
+    here holds clear_cache; ``collate_padded``; the eval-mode attention ``gsat.forward_pass(b, 0, False)[0]`` under ``torch.no_grad()``
+    with every module in ``eval()`` mode; ``explanation_levels`` -- ONE fused ranking over the ``batch_size`` real graphs --;
+    ``explanation_stack``: the ``2 S + 1`` variants of the batch side by side, in a launch count that does not depend on ``S``; ONE
+    ``gsat.clf`` forward WITHOUT ``edge_atten`` on the stack, outside ``padded()`` (eval-mode BatchNorm takes no batch statistics, and the
+    padding rows of every variant sit in that variant's padding graph); and ``log.append`` into a
+    :class:`~dp_gsat_amd.eval_log.FidelityCurveLog` (``log``).  Nothing is read back per batch.
+
+    ``run(graph_ids)`` resets the log, replays every full batch -- ragged: every row of ``batches``, no eager batch --, runs a fixed-count
+    tail eagerly through the same code on ``dataset.collate`` output, and returns ``log.compute()``: ``levels``, ``fidelity_plus``,
+    ``fidelity_minus``, ``p_keep``, ``p_drop``, ``flip_plus``, ``flip_minus``, ``kept_fraction`` (lists over the levels), ``p_full``, ``n``.
+
+    After a step: ``edge_att`` [E_cap, 1], ``edge_level`` uint8[E_cap] (arbitrary at the padding slots), ``stack`` (the
+    ``StackedExplanationBatch``), ``logits`` [(2 S + 1) * (B + 1), C] and ``batch``.  ``overflowed()`` tells (one host read) whether a batch
+    or a variant since the last call did not fit; ``check_epoch`` tells beforehand.
+
+    The graph writes no parameter, buffer or optimizer state and draws from neither the device seed stream nor torch's generators: a curve
+    epoch between ``ReplayedStep`` steps leaves the training run bitwise unchanged.
+
+    Refused with ValueError before anything is captured: what ``ReplayedFidelity`` refuses -- a dataset without graph labels, ``DualGSAT``,
+    ``sync_group`` BatchNorm, the multi-label criterion, a dataset whose largest graph has more edges than ``rank_edges_lds_cap()``, a
+    capacity the first batch does not fit -- and bad levels: neither or both of ``ks`` and ``ratios``, values that are not strictly
+    increasing, more than 16."""
+
+    def __init__(self, gsat, dataset, batch_size: int, ks=None, ratios=None, capacity: Optional[tuple] = None,
+                 max_graphs: Optional[int] = None, graph=None, ragged: bool = False):
+        self.ks, self.ratios = _explain.check_levels(ks, ratios)
+        if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
+            raise ValueError("ReplayedFidelityCurve replays GSAT.forward_pass and its backbone; DualGSAT fidelity is not covered")
+        if getattr(gsat.criterion, "multi_label", False):
+            raise ValueError(_MULTI_LABEL)
+        _refuse_sync_group(gsat)
+        if dataset.y_all is None:
+            raise ValueError("ReplayedFidelityCurve needs a dataset with graph labels (the eval-mode forward takes them); edge labels are "
+                             "not needed")
+        self.max_seg_edges = int(dataset.edge_counts.max()) if dataset.num_graphs else 0          # one host read, here
+        if self.max_seg_edges > _explain.rank_edges_lds_cap():
+            raise ValueError(f"the dataset's largest graph has {self.max_seg_edges} edges, above rank_edges_lds_cap() = "
+                             f"{_explain.rank_edges_lds_cap()}: the captured ranking takes the fused path only")
+        self.gsat, self.dataset = gsat, dataset
+        self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
+        self._max_graphs = dataset.num_graphs if max_graphs is None else int(max_graphs)
+        self._overflow = torch.zeros(1, dtype=torch.int32, device=dataset.x_all.device)
+        self.log = self.batch = self.edge_att = self.edge_level = self.stack = self.logits = None
+        try:
+            _capture_evaluator(self, self._make_log)
+        finally:
+            self._overflow.zero_()
+
+    def _make_log(self):
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        with torch.no_grad(), padded(b.valid, b.capacity):
+            get_index(b.edge_index, int(b.x.shape[0])).graphs(b.batch, int(b.num_graphs))
+            logits = self.gsat.clf(b.x, b.edge_index, b.batch, getattr(b, "edge_attr", None))
+        self.log = FidelityCurveLog(self._max_graphs, int(logits.shape[1]), self.ks, self.ratios, self.dataset.x_all.device)
+
+    def _forward(self, b, epoch=0):
+        """Attention, levels, the stack, the one backbone forward and the append for batch ``b`` -- a ``PaddedBatch`` (the captured body)
+        or ``collate`` output (the eager tail, stacked at the captured batch size); the modules are in eval mode."""
+        with torch.no_grad():
+            att = edge_tensor(self.gsat.forward_pass(b, epoch, False)[0]).detach()
+            valid = getattr(b, "valid", None)
+            stack = explanation_stack(b, att, ks=self.ks, ratios=self.ratios, batch_size=self.batch_size, max_seg_edges=self.max_seg_edges)
+            logits = self.gsat.clf(stack.x, stack.edge_index, stack.batch, stack.edge_attr)
+            over = stack.valid[:, 3].amax().view(1)
+            self._overflow.bitwise_or_(over if valid is None else over | valid[3:4])
+            self.log.append(logits, stack.valid, valid)
+        return att, stack, logits
+
+    def run_once(self):
+        """The body of the captured graph, run on the current stream."""
+        clear_cache()
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        b.r = self.r
+        att, stack, logits = self._forward(b, 0)
+        self._publish(False, batch=b, edge_att=att, edge_level=stack.edge_level, stack=stack, logits=logits)
+
+    def run(self, graph_ids, epoch: int = 0) -> dict:
+        """One curve epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, a
+        fixed-count tail of fewer than ``batch_size`` graphs runs eagerly through the same code, and ``log.compute()`` -- one reduction
+        launch, one host read -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
+        return _run_epoch(self, graph_ids, epoch)
+
+    def overflowed(self) -> bool:
+        """True if a batch or a variant of its stack since the last call (or since capture) did not fit its capacity.  One host read;
+        clears the flag."""
         return _take_overflow(self)

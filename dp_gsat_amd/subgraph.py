@@ -15,6 +15,7 @@ replays inside a captured graph (``ReplayedFidelity``).
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -344,3 +345,150 @@ def explanation_fidelity(clf, data, att, k: Optional[int] = None, ratio: Optiona
         clf.train(was_training)
     return {"logits_full": full, "logits_keep": lk, "logits_drop": ld,
             "fidelity_plus": (p_full - p_drop).mean(), "fidelity_minus": (p_full - p_keep).mean()}
+
+
+# ---- fidelity curves: every sparsity level of a batch in one stacked batch ------------------------------------------------------------------
+def fidelity_stack_block_items() -> int:
+    """Edge slots one workgroup of the stack kernels owns."""
+    return int(_lib.load().gsat_fidelity_stack_block_items())
+
+
+class StackedExplanationBatch(Batch):
+    """The result of :func:`explanation_stack`: a plain batch of ``variants * graphs_per_variant`` graphs -- ``x``, ``edge_index``,
+    ``batch``, ``edge_attr``, ``num_graphs`` -- plus ``valid`` (int32[variants, 4] on the device: N_real, kept edges, graphs, overflow of
+    every variant), ``levels`` (the ``ks`` or ``ratios``) and ``by_ratio``, ``variants`` (``2 * len(levels) + 1``), ``segment_offsets``
+    (host ints: variant ``v`` owns the edge slots ``[segment_offsets[v], segment_offsets[v + 1])``), ``node_capacity`` (variant ``v`` owns
+    the node rows ``[v * node_capacity, (v + 1) * node_capacity)``), ``graphs_per_variant`` (the padding graph last), ``edge_id``
+    (int64[E_stack]: the input's edge slot, -1 for padding) and ``edge_level`` (uint8[E]: :func:`explanation_levels` of the input)."""
+
+    def check(self) -> "StackedExplanationBatch":
+        """One host read of ``valid``: raises ValueError when a variant overflowed (it is then all padding)."""
+        if int(self.valid[:, 3].any()):
+            raise ValueError(_overflow_text((self.node_capacity, "its segment")))
+        return self
+
+
+def explanation_stack(data, att, ks=None, ratios=None, batch_size: Optional[int] = None, *, max_seg_edges: Optional[int] = None,
+                      edge_level: Optional[torch.Tensor] = None) -> StackedExplanationBatch:
+    """Every sparsity level of the explanation ``att`` of ``data`` as ONE batch (gsat_fidelity_stack): with ``S`` levels (``ks`` or
+    ``ratios``, as in :func:`~dp_gsat_amd.explain.explanation_levels`) the ``V = 2 S + 1`` variants "the batch itself", "level s alone"
+    (``v = 1 + s``) and "the batch without level s" (``v = 1 + S + s``) side by side, so that ONE backbone forward scores a whole fidelity
+    curve.  In eval mode the backbone works row by row -- running statistics, no dropout, per-node aggregation, per-graph pools -- so
+    the logits of a graph in the stack are those of the graph on its own up to GEMM rounding.
+
+    ``data``: a ``Batch`` of ``G`` graphs (then ``graphs_per_variant = G + 1``, ``node_capacity = N + 2``, ``E_cap = E``) or a
+    ``PaddedBatch`` (its own ``num_graphs``, node rows and edge slots).  Every variant keeps every node (``drop_isolated=False``) and
+    holds, inside its node rows, graph ids and edge segment, bit for bit what ``edge_subgraph_padded(data, mask_v, (node_capacity,
+    cap_v))`` holds, with ``cap_v = E_cap`` for the full and the drop variants and ``keep_capacity(E_cap, batch_size, k_s | ratio_s)`` for
+    the keep variants (``batch_size`` defaults to the number of real graph slots).  ``x`` is the input's ``x`` (with two zero rows behind
+    an unpadded batch) ``V`` times, ``edge_attr`` is gathered through ``edge_id`` with zero rows in the padding.
+
+    ``max_seg_edges``: the bound that keeps the ranking on the fused path (needed in sync-free mode and under capture); ``edge_level``:
+    levels computed before, in place of ``att``.  Five launches (the levels, four for the stack) besides the ranking, the row gathers
+    and the stack's batch index, whatever ``S`` is, and nothing read back: capturable.  A
+    variant that does not fit, an overflowed input or a bad node id is all padding with ``valid == (0, 0, 0, 1)``: a ValueError after one
+    host read of ``valid`` -- in sync-free mode or under capture nothing is read and ``.check()`` reports it."""
+    from .explain import check_levels, explanation_levels
+    from .replay import keep_capacity
+    ks, ratios = check_levels(ks, ratios)
+    levels = ks if ks is not None else ratios
+    S = len(levels)
+    V = 2 * S + 1
+    x, edge_index, batch = data.x, data.edge_index, data.batch
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    N, E, dev = int(x.shape[0]), int(edge_index.shape[1]), edge_index.device
+    if batch.dtype != torch.int64 or batch.dim() != 1 or int(batch.shape[0]) != N:
+        raise ValueError("batch must be an int64 vector with one entry per node")
+    _need_cuda(x, edge_index, batch, edge_level)
+    capturing = torch.cuda.is_current_stream_capturing()
+    valid_in = getattr(data, "valid", None)
+    if valid_in is not None:
+        if valid_in.dtype != torch.int32 or valid_in.numel() < 4 or not valid_in.is_cuda:
+            raise ValueError("data.valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+        valid_in = valid_in.contiguous()
+        Gp = int(data.num_graphs)
+        real, N_cap = Gp - 1, N
+        if N_cap < 2:
+            raise ValueError("a padded batch has at least two node rows (the padding nodes)")
+    else:
+        real = getattr(data, "num_graphs", None)
+        if real is None:
+            if sync_free() or capturing:
+                raise ValueError("a stack of a batch without num_graphs would read batch.max() back")
+            real = int(batch.max().item()) + 1 if N else 0
+        real = int(real)
+        Gp, N_cap = real + 1, N + 2
+    B = real if batch_size is None else int(batch_size)
+    ei, batch = edge_index.contiguous(), batch.contiguous()
+    if edge_level is None:
+        a = ops.edge_tensor(att)
+        if not isinstance(a, torch.Tensor) or a.numel() != E:
+            raise ValueError(f"attention must have one entry for each of the {E} edges")
+        edge_level = explanation_levels(a, ei, batch, ks=ks, ratios=ratios, num_graphs=Gp if valid_in is not None else real,
+                                        max_seg_edges=max_seg_edges, ranked_graphs=real if max_seg_edges is not None else None)
+    elif edge_level.dtype != torch.uint8 or edge_level.numel() != E:
+        raise ValueError(f"edge_level must be a uint8 tensor with one entry for each of the {E} edges")
+    edge_level = edge_level.reshape(-1).contiguous()
+    caps = [E] + [keep_capacity(E, B, **({"k": l} if ks is not None else {"ratio": l})) for l in levels] + [E] * S
+    offsets = [0]
+    for c in caps:
+        offsets.append(offsets[-1] + int(c))
+    E_stack = offsets[-1]
+    ws_bytes = max(call_size("gsat_fidelity_stack_workspace_bytes", E, S), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    new_ei = torch.empty(2, E_stack, dtype=torch.int64, device=dev)
+    edge_id = torch.empty(E_stack, dtype=torch.int64, device=dev)
+    new_batch = torch.empty(V * N_cap, dtype=torch.int64, device=dev)
+    valid = torch.empty(V, 4, dtype=torch.int32, device=dev)
+    some = lambda t: ptr(t) if t is not None and t.numel() else None
+    call("gsat_fidelity_stack", some(ei), E, N, some(batch), real, ptr(valid_in) if valid_in is not None else None, some(edge_level), S, Gp,
+         N_cap, (ctypes.c_int64 * (V + 1))(*offsets), some(new_ei), some(edge_id), ptr(new_batch), ptr(valid), ptr(ws), ws_bytes, stream())
+    if not (sync_free() or capturing) and int(valid[:, 3].any()):                                   # the one host read
+        raise ValueError(_overflow_text((N_cap, tuple(caps))))
+    if N_cap != N:
+        x = torch.cat([x, x.new_zeros((N_cap - N,) + tuple(x.shape[1:]))])
+    edge_attr = getattr(data, "edge_attr", None)
+    if isinstance(edge_attr, torch.Tensor):
+        _need_cuda(edge_attr)
+        if int(edge_attr.shape[0]) != E:
+            raise ValueError(f"edge_attr has {edge_attr.shape[0]} rows")
+        edge_attr = _take_padded(edge_attr, edge_id)
+    stack = StackedExplanationBatch(x=x.repeat((V,) + (1,) * (x.dim() - 1)), edge_index=new_ei, batch=new_batch, edge_attr=edge_attr,
+                                    y=getattr(data, "y", None), num_graphs=V * Gp, valid=valid, levels=tuple(levels),
+                                    by_ratio=ratios is not None, variants=V, segment_offsets=tuple(offsets), node_capacity=N_cap,
+                                    graphs_per_variant=Gp, edge_id=edge_id, edge_level=edge_level)
+    # a backbone forward on the stack then returns num_graphs rows and never reads batch.max() back
+    get_index(new_ei, V * N_cap).graphs(new_batch, V * Gp)
+    return stack
+
+
+def explanation_fidelity_curve(clf, data, att, ks=None, ratios=None) -> dict:
+    """The fidelity curve of the explanation ``att`` for the backbone ``clf`` over the levels ``ks`` or ``ratios``: eval mode, no grad,
+    :func:`explanation_stack`, ONE ``clf`` forward WITHOUT ``edge_atten`` on the stack.  Returns what ``FidelityCurveLog.compute()``
+    returns, as fp64 device tensors -- ``fidelity_plus`` / ``fidelity_minus`` / ``p_keep`` / ``p_drop`` / ``flip_plus`` / ``flip_minus`` /
+    ``kept_fraction`` of shape [S], ``p_full`` and ``n`` 0-dim -- with ``levels`` and the stacked ``logits [V, graphs_per_variant, C]``."""
+    was_training = clf.training
+    clf.eval()
+    try:
+        with torch.no_grad():
+            stack = explanation_stack(data, att, ks=ks, ratios=ratios)
+            S, V, Gp = len(stack.levels), stack.variants, stack.graphs_per_variant
+            logits = clf(stack.x, stack.edge_index, stack.batch, stack.edge_attr).view(V, Gp, -1)
+            z = logits.double()
+            real = (torch.arange(Gp, device=z.device) < stack.valid[0, 2]).double()          # the padding graph and empty slots count 0
+            n = real.sum()
+            if z.shape[2] > 1:
+                cls = z.argmax(dim=2)
+                p = torch.softmax(z, dim=2).gather(2, cls[0].expand(V, Gp).unsqueeze(2)).squeeze(2)
+            else:
+                cls = (z[:, :, 0] >= 0).long()
+                p = torch.sigmoid(torch.where(cls[0] != 0, 1.0, -1.0) * z[:, :, 0])
+            mean = lambda t: (t * real).sum(dim=-1) / n
+            flips = mean((cls != cls[0]).double())
+            kept = stack.valid[:, 1].double()
+    finally:
+        clf.train(was_training)
+    return {"levels": stack.levels, "fidelity_plus": mean(p[0] - p[1 + S:]), "fidelity_minus": mean(p[0] - p[1:1 + S]), "p_full": mean(p[0]),
+            "p_keep": mean(p[1:1 + S]), "p_drop": mean(p[1 + S:]), "flip_plus": flips[1 + S:], "flip_minus": flips[1:1 + S],
+            "kept_fraction": kept[1:1 + S] / kept[0], "n": n, "logits": logits}

@@ -27,11 +27,16 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
     (``dp_gsat_amd.ReplayedFidelity``): a third captured graph cuts the K best edges of every graph out on the device, runs the backbone
     on the full batch, on the explanation alone and on the batch without it, and logs the probabilities; one host read per epoch.
 
+  * ``--graph [--ragged] --fidelity-curve 0.1,0.2,...`` -- each report line is followed by one line per sparsity level: the fidelity of
+    the top-ratio explanation on the test split at every ratio (``dp_gsat_amd.ReplayedFidelityCurve``).  One captured graph ranks the
+    edges once, stacks the batch, every explanation and every complement into ONE batch and runs the backbone once.
+
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --train-scores
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity 5
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity-curve 0.2,0.5,0.8
 """
 import argparse
 import os
@@ -86,6 +91,8 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="with --graph: budget batches of a ragged graph count, every batch a replay")
     ap.add_argument("--train-scores", action="store_true", help="with --graph --ragged: log the training pass and print its scores")
     ap.add_argument("--fidelity", type=int, default=None, metavar="K", help="with --graph: print the fidelity of the top-K explanation on the test split")
+    ap.add_argument("--fidelity-curve", type=lambda s: [float(v) for v in s.split(",")], default=None, metavar="R1,R2,...",
+                    help="with --graph: print the fidelity of the top-ratio explanation on the test split at every ratio (increasing, in (0, 1])")
     args = ap.parse_args()
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -97,6 +104,8 @@ def main():
         ap.error("--train-scores logs replays of every batch: it needs --graph --ragged")
     if args.fidelity is not None and not args.graph:
         ap.error("--fidelity replays a captured fidelity batch: it needs --graph")
+    if args.fidelity_curve is not None and not args.graph:
+        ap.error("--fidelity-curve replays a captured stacked batch: it needs --graph")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     if world > 1:
@@ -136,7 +145,7 @@ def main():
                                  G.precision_at_k(att, b.edge_label, 5, b.batch, b.edge_index, b.num_graphs).double().mean()]).tolist()
         return acc, auc, prec
 
-    replayed = replayed_eval = replayed_fidelity = None
+    replayed = replayed_eval = replayed_fidelity = replayed_curve = None
     if args.ragged:
         # the budget of a batch: batch_size graphs of the mean size (never less than the largest graph alone); one host read
         slots = min(args.batch_size, len(graphs))
@@ -147,12 +156,16 @@ def main():
         replayed_eval = G.ReplayedEval(gsat, ds, slots, 5, capacity=capacity, ragged=True)
         if args.fidelity is not None:
             replayed_fidelity = G.ReplayedFidelity(gsat, ds, slots, k=args.fidelity, capacity=capacity, ragged=True)
+        if args.fidelity_curve is not None:
+            replayed_curve = G.ReplayedFidelityCurve(gsat, ds, slots, ratios=args.fidelity_curve, capacity=capacity, ragged=True)
     elif args.graph and n_train >= args.batch_size:
         replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
     if args.graph and not args.ragged:
         replayed_eval = G.ReplayedEval(gsat, ds, min(args.batch_size, len(graphs)), 5)
         if args.fidelity is not None:
             replayed_fidelity = G.ReplayedFidelity(gsat, ds, min(args.batch_size, len(graphs)), k=args.fidelity)
+        if args.fidelity_curve is not None:
+            replayed_curve = G.ReplayedFidelityCurve(gsat, ds, min(args.batch_size, len(graphs)), ratios=args.fidelity_curve)
 
     def evaluate_replayed(ids, epoch):
         res = replayed_eval.run(ids, epoch)      # full batches: replays; the tail: eager (--ragged: a replay too); one scoring pass at the end
@@ -197,6 +210,12 @@ def main():
                 res = replayed_fidelity.run(test_ids)
                 print(f"      fidelity@{args.fidelity}  fidelity_plus {res['fidelity_plus']:.4f}  fidelity_minus {res['fidelity_minus']:.4f}  "
                       f"flip_plus {res['flip_plus']:.3f}  flip_minus {res['flip_minus']:.3f}", flush=True)
+            if replayed_curve is not None:                        # every level from ONE ranking and ONE backbone forward per batch
+                res = replayed_curve.run(test_ids)
+                for s, ratio in enumerate(res["levels"]):
+                    print(f"      fidelity@{ratio:g}  kept {res['kept_fraction'][s]:.3f}  fidelity_plus {res['fidelity_plus'][s]:.4f}  "
+                          f"fidelity_minus {res['fidelity_minus'][s]:.4f}  flip_plus {res['flip_plus'][s]:.3f}  "
+                          f"flip_minus {res['flip_minus'][s]:.3f}", flush=True)
             if args.train_scores:                                 # scored from what the replays of this epoch logged: no eager batch
                 res = replayed.epoch_scores()
                 print(f"      train  loss {res['loss']:.4f}  pred {res['pred']:.4f}  info {res['info']:.4f}  acc {res['clf_acc']:.3f}  "

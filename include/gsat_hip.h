@@ -983,6 +983,79 @@ int gsat_fidelity_reduce(const int32_t* log_cls, const double* log_p, const int6
 /* log_state = (0, 0, 0, 0), by a kernel (no memset node). */
 int gsat_fidelity_reset(int64_t* log_state, void* stream);
 
+/* ================================= fidelity curves: the stacked batch ======================== */
+
+/*
+ * The sparsity levels of a fidelity curve from ONE ranking.  rank int32[E] (gsat_rank_edges: position of an edge inside its graph),
+ * edge_ptr int32[G + 1] and edge_graph int32[E] (the graph of every edge) on the device; ks int64[levels] OR ratios double[levels] in
+ * HOST memory, exactly one of them, strictly increasing, ks >= 1, ratios in (0, 1], 1 <= levels <= 16 (GSAT_ERR_ARG otherwise).
+ * Level s keeps, per graph of E_g edges, the edges with rank < min(k_s, E_g), or rank < ceil((double)E_g * ratio_s) evaluated in fp64
+ * without contraction.  level uint8[E] = the smallest s that keeps the edge, `levels` when none does -- so `level <= s` is the top-k_s
+ * (top-ratio_s) mask, bit for bit.  An edge whose graph id is outside [0, G) -- the padding graph of a padded batch when G counts the
+ * ranked graphs -- gets `levels`, and its rank is not read.  One launch, capturable.  E, G < 2^31 (GSAT_ERR_UNSUPPORTED otherwise).
+ */
+int gsat_fidelity_levels(const int32_t* rank, const int32_t* edge_ptr, const int32_t* edge_graph, int64_t E, int64_t G, const int64_t* ks,
+                         const double* ratios, int64_t levels, uint8_t* level, void* stream);
+
+/*
+ * The V = 2 * levels + 1 padded extractions of a fidelity curve, side by side in one batch: variant 0 is the batch itself, variant
+ * 1 + s keeps the edges with level <= s, variant 1 + levels + s keeps those with level > s; every node is kept in every variant.
+ * Input: edge_index int64[2, E], batch int64[N], valid_in int32[4] (nullable; N_real, E_real, graphs, overflow of a padded batch --
+ * rows and slots at or beyond its counts are never read), level uint8[E] (values above `levels` count as `levels`), G the number of
+ * real graphs of an input without valid_in.
+ * Variant v owns the node rows [v * cap_nodes, (v + 1) * cap_nodes), cap_nodes >= max(N, 2), the graph ids [v * graphs_per_variant,
+ * (v + 1) * graphs_per_variant) with the padding graph last, and the edge slots [segment_offsets[v], segment_offsets[v + 1]);
+ * segment_offsets int64[V + 1] in HOST memory, starting at 0, non-decreasing; E_stack = segment_offsets[V].  Inside its segment a
+ * variant holds what gsat_subgraph_padded (edge mode, every node kept) gives for its mask at the capacity (cap_nodes, segment length),
+ * with node ids moved by v * cap_nodes:
+ *   out_edge_index int64[2, E_stack], out_edge_id int64[E_stack]   kept edges in their order and their slots in the input, then the
+ *                                                                   slack as padding edges among the variant's padding nodes, id -1
+ *   out_batch int64[V * cap_nodes]   v * graphs_per_variant + batch[i] for the variant's real rows -- every row when valid_in is given
+ *                                    and cap_nodes == N, where gsat_subgraph_padded's caller shares the input's rows --, the variant's
+ *                                    padding graph for the rest
+ *   valid_out int32[V, 4]            (N_real, kept edges, graphs, 0)
+ * A variant that does not fit (N_real + 2 > cap_nodes, more kept edges than its segment), an input whose valid_in[3] is set or an edge
+ * with a node id outside [0, N_real) -- then every variant -- is all padding with (0, 0, 0, 1).  Nothing is written out of bounds.
+ * 4 launches whatever `levels` is (per-workgroup counts per level bin; one workgroup scans them; scatter; fill), kernels only, no
+ * atomics, nothing read back: capturable and bitwise repeatable.  Each workgroup owns gsat_fidelity_stack_block_items() edge slots.
+ * workspace: gsat_fidelity_stack_workspace_bytes(E, levels).  Every extent, V * cap_nodes and V * graphs_per_variant < 2^31
+ * (GSAT_ERR_UNSUPPORTED otherwise).
+ * replaces: 2 * levels calls of gsat_subgraph_padded (5 launches each) and as many backbone forwards by one stacked forward.
+ */
+int64_t gsat_fidelity_stack_block_items(void);
+size_t gsat_fidelity_stack_workspace_bytes(int64_t E, int64_t levels);
+int gsat_fidelity_stack(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* batch, int64_t G, const int32_t* valid_in,
+                        const uint8_t* level, int64_t levels, int64_t graphs_per_variant, int64_t cap_nodes, const int64_t* segment_offsets,
+                        int64_t* out_edge_index, int64_t* out_edge_id, int64_t* out_batch, int32_t* valid_out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/*
+ * gsat_fidelity_append with a level axis.  logits fp32[V * graphs_per_variant, classes], V = 2 * levels + 1: the backbone on a stacked
+ * batch, block v being variant v.  valid int32[4] (nullable): the input batch's word; stack_valid int32[V, 4]: the stack's.  The graph
+ * count g is clamp(valid[2], 0, graphs_per_variant), without valid the full variant's stack_valid[0][2].  log_state int64[20] =
+ * (graphs, batches, flags, real edges, kept edges of level 0 .. 15).  Two launches: the rows, then one thread that advances log_state.
+ * Per graph i < g at slot g0 + i, with c = the class of row i of block 0:
+ *   log_cls int32[max_graphs, V]   the class predicted from every block
+ *   log_p  double[max_graphs, V]   the probability of c under every block
+ * by the class and probability rules of gsat_fidelity_append.  The commit adds stack_valid[0][1] to the real edges and
+ * stack_valid[1 + s][1] to the kept edges of level s.  A batch whose valid[3] or any stack_valid[v][3] is set appends nothing and sets
+ * flag bit 0; one that would exceed max_graphs appends nothing and sets flag bit 1.
+ */
+int gsat_fidelity_curve_append(const float* logits, int64_t graphs_per_variant, int64_t classes, int64_t levels, const int32_t* valid,
+                               const int32_t* stack_valid, int32_t* log_cls, double* log_p, int64_t* log_state, int64_t max_graphs,
+                               void* stream);
+
+/*
+ * One launch of one workgroup: out int64[5 + 7 * levels] = (graphs, batches, flags, real edges), kept edges [levels], #(cls_drop_s !=
+ * cls_full) [levels], #(cls_keep_s != cls_full) [levels], then the bit patterns of doubles: the sum of p_full, and [levels] each of the
+ * sums of p_keep_s, p_drop_s, p_full - p_drop_s, p_full - p_keep_s.  fp64 sums in a fixed order: bitwise repeatable.
+ */
+int gsat_fidelity_curve_reduce(const int32_t* log_cls, const double* log_p, const int64_t* log_state, int64_t max_graphs, int64_t levels,
+                               int64_t* out, void* stream);
+
+/* log_state int64[20] = 0, by a kernel (no memset node). */
+int gsat_fidelity_curve_reset(int64_t* log_state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
