@@ -73,6 +73,8 @@ SIGNATURES = {
     "gsat_gemm_bf16x3": (INT, [INT, INT, I64, I64, I64, P, I64, P, I64, P, I64, P, INT, P, SZ, P]),
     "gsat_gemm_wgrad_plan": (INT, [I64, I64, I64, P]),
     "gsat_gemm_wgrad_x3": (INT, [I64, I64, I64, P, I64, P, I64, P, I64, INT, P, SZ, P]),
+    "gsat_gemm_pair_plan": (INT, [I64, I64, I64, I64, P]),
+    "gsat_gemm_pair_x3": (INT, [I64, I64, I64, I64, P, I64, P, I64, P, I64, P, I64, P, I64, INT, P, SZ, P]),
     "gsat_attn_fwd_workspace_bytes": (SZ, [P]),
     "gsat_attn_fwd_kind": (I32, [P]),
     "gsat_attn_bwd_workspace_bytes": (SZ, [P]),

@@ -41,6 +41,11 @@ static int gemm_rm(hipStream_t stream, bool ta, bool tb, int64_t M, int64_t N, i
     if (ta && !tb && split_ok && bwd_split) return gemm_wgrad(stream, M, N, K, A, lda, B, ldb, C, ldc, beta != 0.f, ws.ptr, ws.floats, defer);
     return gemm_f32(stream, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, nullptr, beta != 0.f, ws.ptr, ws.floats, split_ok && bwd_split, defer);
 }
+// whether the backward's OUT[R,Co] = G W and DW[Cg,Cy] = G^T Y go out as one launch (gemm_pair_x3): the split-bf16 leg only
+static bool pair_ok(int64_t R, int64_t Cg, int64_t Co, int64_t Cy) {
+    const char* env = getenv("GSAT_ATTN_BWD_SPLIT");
+    return !(env && atoi(env) == 0) && gemm_pair_plan(R, Cg, Co, Cy).paired;
+}
 
 // ------------------------------------------------------------------------------------------------
 // pre-activation sources: dense rows (node mode / layer 2) or P[src]+Q[dst] (edge mode layer 1)
@@ -963,6 +968,8 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
     // dW2[C2,C1] = dh2^T a1 ; da1[M,C1] = dh2 W2
     if (dual_gemm_ok(1, M, C2, C1, C1)) {            // both products in one pass over dh2 (dual_gemm.hip)
         if ((rc = dual_gemm(stream, 1, M, C2, C1, C1, dh2, C2, a->a1, C1, a->W2, C1, da1, C1, 0, gr->dW2, C1, dws, dws_bytes))) return rc;
+    } else if (pair_ok(M, C2, C1, C1)) {             // both products in one launch, each on its own kernel body (gemm.hip: k_pair_x3)
+        if ((rc = gemm_pair_x3(stream, M, C2, C1, C1, dh2, C2, a->W2, C1, da1, C1, a->a1, C1, gr->dW2, C1, false, gws.ptr, gws.floats, &jobs[0]))) return rc;
     } else {
         if ((rc = gemm_rm(stream, true, false, C2, C1, M, dh2, C2, a->a1, C1, 0.f, gr->dW2, C1, gws, true, &jobs[0]))) return rc;
         if ((rc = gemm_rm(stream, false, false, M, C1, C2, dh2, C2, a->W2, C1, 0.f, da1, C1, GemmWs{nullptr, 0}, true))) return rc;
@@ -1015,6 +1022,8 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
         }
         if (dual_gemm_ok(2, N, C1, H, H)) {
             if ((rc = dual_gemm(stream, 2, N, C1, H, H, da1, C1, a->emb, H, a->W1, H, gr->demb, H, 0, gr->dW1, H, dws, dws_bytes))) return rc;
+        } else if (pair_ok(N, C1, H, H)) {
+            if ((rc = gemm_pair_x3(stream, N, C1, H, H, da1, C1, a->W1, H, gr->demb, H, a->emb, H, gr->dW1, H, false, gws1.ptr, gws1.floats, &jobs[1]))) return rc;
         } else {
         if ((rc = gemm_rm(stream, false, false, N, H, C1, da1, C1, a->W1, H, 0.f, gr->demb, H, GemmWs{nullptr, 0}, true))) return rc;
         if ((rc = gemm_rm(stream, true, false, C1, H, N, da1, C1, a->emb, H, 0.f, gr->dW1, H, gws1, true, &jobs[1]))) return rc;

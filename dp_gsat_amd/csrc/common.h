@@ -71,6 +71,13 @@ WgradPlan wgrad_plan(int64_t Mo, int64_t No, int64_t K);
 size_t gemm_wgrad_workspace_floats(int64_t Mo, int64_t No, int64_t K);
 int gemm_wgrad(hipStream_t stream, int64_t Mo, int64_t No, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
                int64_t ldc, bool accumulate, float* ws, size_t ws_floats, SlabJob* defer = nullptr);
+// the two products of the extractor backward that read one gradient G [R,Cg], OUT[R,Co] = G W and DW[Cg,Cy] (+)= G^T Y, as ONE launch
+// (gemm.hip: k_pair_x3) where the plan pairs them, else as gemm_wgrad + gemm_f32; the plan is host arithmetic
+struct PairPlan { int paired, wgrad_blocks, dgrad_blocks, lds_bytes; };
+PairPlan gemm_pair_plan(int64_t R, int64_t Cg, int64_t Co, int64_t Cy);
+int gemm_pair_x3(hipStream_t stream, int64_t R, int64_t Cg, int64_t Co, int64_t Cy, const float* G, int64_t ldg, const float* W, int64_t ldw,
+                 float* OUT, int64_t ldo, const float* Y, int64_t ldy, float* DW, int64_t lddw, bool accumulate, float* ws, size_t ws_floats,
+                 SlabJob* defer = nullptr);
 
 // ---- gather-sum over a CSR (aggregate.hip), reused by the extractor backward -------------------------
 int aggr_sum_fwd_impl(hipStream_t stream, const float* x, const float* self_rows, const float* att, const float* edge_emb,

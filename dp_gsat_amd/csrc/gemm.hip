@@ -73,13 +73,18 @@ __device__ __forceinline__ void store_kmajor(const StageKC& s, float* __restrict
 // The remap hands every XCD a contiguous range of the linear tile list: tiles that share an operand slab run on the same
 // L2, back to back (post_nn dW 86 -> 79 us, c5s layer 2 978 -> 906 us; GSAT_GEMM_XCD=0 switches it off for comparison).
 __device__ int GEMM_XCD_REMAP_ON = 1;
-__device__ __forceinline__ void gemm_tile_coords(int& bx, int& by, int& bz) {
-    const unsigned gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
-    const unsigned L = (blockIdx.z * gy + blockIdx.y) * gx + blockIdx.x;
-    if (!GEMM_XCD_REMAP_ON) { bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z; return; }
-    const unsigned q = total >> 3, r = total & 7, xcd = L & 7, i = L >> 3;
-    const unsigned t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
+// (linear block id L of a gx x gy x gz grid: a kernel that carries two grids in one launch passes a virtual id, k_pair_x3)
+__device__ __forceinline__ void gemm_tile_coords(unsigned L, unsigned gx, unsigned gy, unsigned gz, int& bx, int& by, int& bz) {
+    const unsigned total = gx * gy * gz;
+    unsigned t = L;
+    if (GEMM_XCD_REMAP_ON) {
+        const unsigned q = total >> 3, r = total & 7, xcd = L & 7, i = L >> 3;
+        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
+    }
     bx = (int)(t % gx); by = (int)((t / gx) % gy); bz = (int)(t / (gx * gy));
+}
+__device__ __forceinline__ void gemm_tile_coords(int& bx, int& by, int& bz) {
+    gemm_tile_coords((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x, gridDim.y, gridDim.z, bx, by, bz);
 }
 
 template <bool A_T, bool B_T, int TM, int TN>
@@ -586,10 +591,16 @@ __global__ __launch_bounds__(WS_THREADS, (KR <= 64 && NQ <= 4) ? 4 : 2) void k_g
 // planes of a double-buffered LDS image, every wave then reads its operand fragments with one ds_read_b128 per plane and step.  The MFMA
 // time is a third of the fp32 kernel's, so the launch is bound by its HBM traffic.  k-splits meet in LDS in fixed order.
 // ================================================================================================================
-template <bool B_T, int KSTEPS, int NQ>
-__global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
-                                                             float* __restrict__ C, int64_t ldc, int M, int N, int K, int NB, int accumulate, int tiles) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char wx_lds[];
+// The body takes its place in the grid as arguments (workgroup bx of gx walks the row tiles, by is the 256-column chunk) and its LDS as a
+// pointer, so that k_pair_x3 can run it next to the weight gradient's body in one launch.
+// KFIX: K and NB are taken from the template arguments (K = 64 NQ, K / (8 / NB) = 16 KSTEPS, as the dispatcher chose them), which turns the
+// staging indices and LDS strides into constants: registers that k_pair_x3 needs to stay within the 128 of two workgroups per CU (not for
+// its instances with four or eight k-splits, whose exchange loop then unrolls into more registers than it saves).  Same arithmetic.
+template <bool B_T, int KSTEPS, int NQ, bool KFIX = false>
+__device__ __forceinline__ void gemm_ws_x3_body(unsigned char* wx_lds, int bx, int by, int gx, const float* __restrict__ A, int64_t lda,
+                                                const float* __restrict__ B, int64_t ldb, float* __restrict__ C, int64_t ldc, int M, int N, int K_,
+                                                int NB_, int accumulate, int tiles) {
+    const int K = KFIX ? 64 * NQ : K_, NB = KFIX ? 2 * KSTEPS / NQ : NB_;
     const int RS = 2 * K + 16;                               // bytes per row of one plane
     const int PLANE = WS_ROWS * RS;
     unsigned char* const buf0 = wx_lds;                      // [hi plane | lo plane]
@@ -597,7 +608,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __res
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int cb = wave % NB, ks = wave / NB, KS = 8 / NB;
     const int c = lane & 31, h = lane >> 5;
-    const int n0 = blockIdx.y * (NB * 32) + cb * 32;
+    const int n0 = by * (NB * 32) + cb * 32;
     const int kw0 = ks * (KSTEPS * 16);                      // first k of this wave's range
     // ---- this wave's share of B -> hi / lo fragments in registers (once): lane (c, h) holds k = kw0 + 16 s + 8 h + j of column n0 + c ----
     bf16x8 bh[KSTEPS], bl[KSTEPS];
@@ -630,31 +641,40 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __res
         srow[p] = idx / K4;
         soff[p] = 4 * (idx % K4);
     }
-    float4 st[NQ];
-    auto gload = [&](int tile) {
+    // HALVES (k_pair_x3<8, 4> only): the tile is staged as two halves through NQ / 2 registers -- the first half goes to LDS in the middle
+    // of the tile's MFMAs (the other buffer is free from the top of the round) and its registers take the second half
+    constexpr bool HALVES = KFIX && NQ == 4 && KSTEPS == 8;
+    constexpr int NS = HALVES ? NQ / 2 : NQ;
+    float4 st[NS];
+    auto gload = [&](int tile, int half = 0) {
         const int m0 = tile * WS_ROWS;
 #pragma unroll
-        for (int p = 0; p < NQ; ++p) st[p] = ld4(A + (size_t)min(m0 + srow[p], M - 1) * lda + soff[p]);       // rows past M: clamped, never stored
+        for (int p = 0; p < NS; ++p)         // rows past M: clamped, never stored
+            st[p] = ld4(A + (size_t)min(m0 + srow[p + half * NS], M - 1) * lda + soff[p + half * NS]);
     };
-    auto lstore = [&](unsigned char* dst) {
+    auto lstore = [&](unsigned char* dst, int half = 0) {
 #pragma unroll
-        for (int p = 0; p < NQ; ++p) {
+        for (int p = 0; p < NS; ++p) {
             const float4 v = st[p];
+            const int o = srow[p + half * NS] * RS + soff[p + half * NS] * 2;
             const uint2 H = make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w));
             const uint2 L = make_uint2(pack_bf16(v.x - bf16_hi(v.x), v.y - bf16_hi(v.y)), pack_bf16(v.z - bf16_hi(v.z), v.w - bf16_hi(v.w)));
-            *reinterpret_cast<uint2*>(dst + srow[p] * RS + soff[p] * 2) = H;
-            *reinterpret_cast<uint2*>(dst + PLANE + srow[p] * RS + soff[p] * 2) = L;
+            *reinterpret_cast<uint2*>(dst + o) = H;
+            *reinterpret_cast<uint2*>(dst + PLANE + o) = L;
         }
     };
-    int tile = blockIdx.x;
-    if (tile < tiles) { gload(tile); lstore(buf0); }
+    int tile = bx;
+    if (tile < tiles) {
+        gload(tile); lstore(buf0);
+        if (HALVES) { gload(tile, 1); lstore(buf0, 1); }
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0): B is in registers now (see k_gemm_ws)
     __syncthreads();
     unsigned char* cur = buf0;
     unsigned char* nxt = buf1;
     const bool col_ok = n0 + c < N;
-    for (; tile < tiles; tile += gridDim.x) {
-        const int ntile = tile + gridDim.x;
+    for (; tile < tiles; tile += gx) {
+        const int ntile = tile + gx;
         if (ntile < tiles) gload(ntile);
         f32x16 acc;
 #pragma unroll
@@ -668,6 +688,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __res
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s_], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s_], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s_], acc, 0, 0, 0);
+            if (HALVES && s_ == KSTEPS / 2 - 1 && ntile < tiles) { lstore(nxt); gload(ntile, 1); }
         }
         float* const xch = reinterpret_cast<float*>(cur);
         if (KS > 1) {
@@ -678,7 +699,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __res
                 for (int r = 0; r < 16; ++r) part[r * 64 + lane] = acc[r];
             }
         }
-        if (ntile < tiles) lstore(nxt);
+        if (ntile < tiles) lstore(nxt, HALVES ? 1 : 0);
         __syncthreads();
         if (ks == 0) {
             if (KS > 1) {
@@ -704,6 +725,12 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __res
         if (KS > 1) __syncthreads();
         unsigned char* tmp = cur; cur = nxt; nxt = tmp;
     }
+}
+template <bool B_T, int KSTEPS, int NQ>
+__global__ __launch_bounds__(WS_THREADS, 2) void k_gemm_ws_x3(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                                             float* __restrict__ C, int64_t ldc, int M, int N, int K, int NB, int accumulate, int tiles) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char wx_lds[];
+    gemm_ws_x3_body<B_T, KSTEPS, NQ>(wx_lds, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, A, lda, B, ldb, C, ldc, M, N, K, NB, accumulate, tiles);
 }
 
 // out[i] = (accumulate ? out[i] : 0) + sum_s slabs[s][i].  Eight independent partial sums (slab s goes to
@@ -904,6 +931,11 @@ static bool wsx3_applicable(int64_t M, int64_t N, int64_t K) {
     int nb, st;
     return on && M >= 8192 && M < (1ll << 31) - 64 && wsx3_geometry(N, K, &nb, &st);
 }
+// `accumulate` argument of the kernel: bit 0 adds to C, bit 1: streaming output (too large for the caches to keep until its consumer runs)
+static int wsx3_out_flag(bool accumulate, int64_t M, int64_t N) {
+    static const int nt_mode = getenv("GSAT_GEMM_NT") ? atoi(getenv("GSAT_GEMM_NT")) : 1;
+    return (accumulate ? 1 : 0) | ((nt_mode && !accumulate && (size_t)M * N * 4 >= ((size_t)64 << 20)) ? 2 : 0);
+}
 template <bool B_T, int KSTEPS, int NQ>
 static int wsx3_launch(hipStream_t stream, dim3 grid, size_t lds, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                        int M, int N, int K, int nb, int accumulate, int tiles) {
@@ -924,9 +956,7 @@ static int gemm_wsx3(hipStream_t stream, bool b_t, int64_t M, int64_t N, int64_t
     const int per_cu = (2 * lds <= 150 * 1024 && st * 8 + nq * 9 <= 84) ? 2 : 1;      // two workgroups per CU need <= 128 registers (fragments + staging)
     const int chunks = (int)ceil_div(N, 256);
     const dim3 grid((unsigned)std::min<int64_t>(tiles, std::max<int64_t>(1, (int64_t)256 * per_cu / chunks)), (unsigned)chunks);
-    // bit 1: streaming output (too large for the caches to keep until its consumer runs)
-    static const int nt_mode = getenv("GSAT_GEMM_NT") ? atoi(getenv("GSAT_GEMM_NT")) : 1;
-    const int acc_flag = (accumulate ? 1 : 0) | ((nt_mode && !accumulate && (size_t)M * N * 4 >= ((size_t)64 << 20)) ? 2 : 0);
+    const int acc_flag = wsx3_out_flag(accumulate, M, N);
 #define XGO(BT, S, Q) return wsx3_launch<BT, S, Q>(stream, grid, lds, A, lda, B, ldb, C, ldc, (int)M, (int)N, (int)K, nb, acc_flag, tiles)
 #define XQ(BT, S) do { switch (nq) { case 1: XGO(BT, S, 1); case 2: XGO(BT, S, 2); case 4: XGO(BT, S, 4); case 8: XGO(BT, S, 8); default: break; } } while (0)
 #define XS(BT) do { switch (st) { case 2: XQ(BT, 2); break; case 4: XQ(BT, 4); break; default: XQ(BT, 8); break; } } while (0)
@@ -1090,14 +1120,15 @@ constexpr int WG_MIN_SLABS = 8;                             // fewest 32-row sla
 
 // (A, B and ws are NOT __restrict__: the barrier's fence then keeps every load on its side of it; with noalias operands the compiler moved
 // the prologue's loads of slabs 1 and 2 behind the first barrier)
-__global__ __launch_bounds__(WG_T) void k_wgrad_x3(const float* A, int64_t lda, const float* B, int64_t ldb, float* ws, int Mo, int No, int K,
-                                                   int rows_per) {
+// The body takes its linear block id in a gx x gy x gz grid and its 2 * WG_BUF bytes of LDS as arguments (k_pair_x3 runs it next to the
+// backward-data body in one launch).
+__device__ __forceinline__ void wgrad_x3_body(unsigned char* lds, unsigned L, unsigned gx, unsigned gy, unsigned gz, const float* A, int64_t lda,
+                                              const float* B, int64_t ldb, float* ws, int Mo, int No, int K, int rows_per) {
     constexpr int EP_LD = 36;
     static_assert(2 * WG_BUF >= 8 * 32 * EP_LD * 4, "epilogue staging must fit in the operand planes");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * WG_BUF];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     int bx, by, bz;
-    gemm_tile_coords(bx, by, bz);
+    gemm_tile_coords(L, gx, gy, gz, bx, by, bz);
     const int m0 = by * WG_TILE, n0 = bx * WG_TILE;
     const int kbeg = bz * rows_per, kend = min(K, kbeg + rows_per);          // never empty: S = ceil(K / rows_per)
     const int nslab = (kend - kbeg + GK - 1) / GK;
@@ -1197,6 +1228,38 @@ __global__ __launch_bounds__(WG_T) void k_wgrad_x3(const float* A, int64_t lda, 
         __builtin_amdgcn_wave_barrier();
     }
 }
+__global__ __launch_bounds__(WG_T) void k_wgrad_x3(const float* A, int64_t lda, const float* B, int64_t ldb, float* ws, int Mo, int No, int K,
+                                                   int rows_per) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * WG_BUF];
+    wgrad_x3_body(lds, (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x, gridDim.y, gridDim.z, A, lda, B, ldb, ws, Mo, No, K,
+                  rows_per);
+}
+
+// ================================================================================================================
+// One launch for the two products that read the same gradient G [R, Cg] in the extractor backward: OUT[R, Co] = G W (the body of
+// k_gemm_ws_x3<false>) and the partial tiles of DW[Cg, Cy] = G^T Y (the body of k_wgrad_x3).  Each of the two kernels alone is one 8-wave
+// workgroup per CU with nothing to hide its loads behind; here a workgroup of each kind fits a CU at the same time (128 registers, two
+// LDS images), the dependent boundary between the two launches is gone and the second read of G is a cache hit.  Nothing but the CU is
+// shared: both bodies run unchanged, so every result has the bits of the separate launches.
+//   Linear block L: role (L >> 3) & 1 (0 = weight gradient), virtual id ((L >> 4) << 3) | (L & 7) -- workgroups go to the 8 XCDs
+// round-robin (L & 7), so every XCD gets both roles and the virtual id keeps the XCD of the linear one, which is what the weight
+// gradient's tile remap (gemm_tile_coords) rests on.  `both` (a multiple of 8) ids of each role interleave like this; the blocks behind
+// them take what is left of the weight gradient's grid, then of the backward-data grid.
+// ================================================================================================================
+struct PairWgrad { const float* Y; int64_t ldy; float* ws; int Cy, rows_per; unsigned gx, gy, gz; };
+template <int KSTEPS, int NQ>
+__global__ __launch_bounds__(WG_T, 4) void k_pair_x3(const float* G, int64_t ldg, const float* W, int64_t ldw, float* OUT, int64_t ldo, int R, int Cg,
+                                                     int Co, int NB, int out_flag, int tiles, unsigned dgx, unsigned both, const PairWgrad wg) {
+    static_assert(WG_T == WS_THREADS, "both bodies run on the same workgroup size");
+    extern __shared__ __attribute__((aligned(16))) unsigned char pair_lds[];
+    const unsigned L = blockIdx.x, nw = wg.gx * wg.gy * wg.gz;
+    unsigned role, V;
+    if (L < 2 * both) { role = (L >> 3) & 1; V = ((L >> 4) << 3) | (L & 7); }
+    else if (L - 2 * both < nw - both) { role = 0; V = L - both; }
+    else { role = 1; V = L - nw; }
+    if (role == 0) wgrad_x3_body(pair_lds, V, wg.gx, wg.gy, wg.gz, G, ldg, wg.Y, wg.ldy, wg.ws, Cg, wg.Cy, R, wg.rows_per);
+    else gemm_ws_x3_body<false, KSTEPS, NQ, KSTEPS == 8 || NQ == 2>(pair_lds, (int)(V % dgx), (int)(V / dgx), (int)dgx, G, ldg, W, ldw, OUT, ldo, R, Co, Cg, NB, out_flag, tiles);
+}
 
 // CUs of the current device, asked once (256 on an MI355X, which is also the answer where no device is present: the plan is host arithmetic)
 static int device_cus() {
@@ -1255,6 +1318,83 @@ int gemm_wgrad(hipStream_t stream, int64_t Mo, int64_t No, int64_t K, const floa
     k_wgrad_x3<<<grid, WG_T, 0, stream>>>(A, lda, B, ldb, ws, (int)Mo, (int)No, (int)K, p.rows);
     GSAT_LAUNCH_CHECK();
     const SlabJob job{ws, p.S, (size_t)Mo * No, (int)Mo, (int)No, ldc, accumulate ? 1 : 0, C};
+    if (defer) { *defer = job; return GSAT_OK; }
+    return slab_reduce_jobs(stream, &job, 1);
+}
+
+// Whether OUT[R,Co] = G W and DW[Cg,Cy] = G^T Y run as ONE launch (k_pair_x3): exactly when the first would run on k_gemm_ws_x3, the second
+// on k_wgrad_x3 (both include the split-bf16 setting), two workgroups' LDS fits a CU and GSAT_GEMM_PAIR is not 0.  Host arithmetic and
+// environment reads only.
+PairPlan gemm_pair_plan(int64_t R, int64_t Cg, int64_t Co, int64_t Cy) {
+    static const int on = getenv("GSAT_GEMM_PAIR") ? atoi(getenv("GSAT_GEMM_PAIR")) : 1;
+    PairPlan pp{};
+    if (R <= 0 || Cg <= 0 || Co <= 0 || Cy <= 0 || Cg % 4 != 0 || Co % 4 != 0) return pp;
+    const GemmPlan g = gemm_plan(true, false, false, R, Co, Cg, false, false, Co);
+    const WgradPlan w = wgrad_plan(Cg, Cy, R);
+    if (!on || g.family != GEMM_WS_X3 || !w.eligible) return pp;
+    // Two workgroups must fit the 160 KB of LDS of a CU, or nothing runs side by side: that leaves Cg = 128 and 256 (whole 128-row tiles of
+    // DW; 512 needs 133 KB), whose backward-data geometries are the five (KSTEPS, NQ) that k_pair_x3 is instantiated for (gemm_pair_x3)
+    const size_t lds = std::max<size_t>(2 * WG_BUF, (size_t)4 * WS_ROWS * (2 * Cg + 16));
+    if (2 * lds > (size_t)160 * 1024) return pp;
+    const int64_t chunks = ceil_div(Co, 256), tiles = ceil_div(R, WS_ROWS);
+    pp.paired = 1;
+    pp.wgrad_blocks = (int)((Cg / WG_TILE) * (Cy / WG_TILE) * w.S);
+    pp.dgrad_blocks = (int)(std::min<int64_t>(tiles, std::max<int64_t>(1, device_cus() / chunks)) * chunks);      // one workgroup per CU
+    pp.lds_bytes = (int)lds;
+    return pp;
+}
+
+template <int KSTEPS, int NQ>
+static int pair_launch(hipStream_t stream, unsigned blocks, size_t lds, const float* G, int64_t ldg, const float* W, int64_t ldw, float* OUT, int64_t ldo,
+                       int R, int Cg, int Co, int nb, int out_flag, int tiles, unsigned dgx, unsigned both, const PairWgrad& wg) {
+    static size_t allowed = 64 * 1024;
+    if (lds > allowed) {
+        GSAT_CHECK_HIP(hipFuncSetAttribute((const void*)k_pair_x3<KSTEPS, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        allowed = lds;
+    }
+    k_pair_x3<KSTEPS, NQ><<<blocks, WG_T, lds, stream>>>(G, ldg, W, ldw, OUT, ldo, R, Cg, Co, nb, out_flag, tiles, dgx, both, wg);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+// OUT[R,Co] = G W (G [R,Cg], W [Cg,Co]) and DW[Cg,Cy] (+)= G^T Y (Y [R,Cy]) in one launch where gemm_pair_plan() pairs them, else as the
+// two separate calls.  `defer` as in gemm_wgrad: the ordered sum of DW's partial tiles is left to the caller's slab_reduce_jobs.
+int gemm_pair_x3(hipStream_t stream, int64_t R, int64_t Cg, int64_t Co, int64_t Cy, const float* G, int64_t ldg, const float* W, int64_t ldw,
+                 float* OUT, int64_t ldo, const float* Y, int64_t ldy, float* DW, int64_t lddw, bool accumulate, float* ws, size_t ws_floats,
+                 SlabJob* defer) {
+    const PairPlan pp = gemm_pair_plan(R, Cg, Co, Cy);
+    if (!pp.paired) {
+        const int rc = gemm_wgrad(stream, Cg, Cy, R, G, ldg, Y, ldy, DW, lddw, accumulate, ws, ws_floats, defer);
+        if (rc) return rc;
+        return gemm_f32(stream, false, false, R, Co, Cg, G, ldg, W, ldw, OUT, ldo, nullptr, false, nullptr, 0, true);
+    }
+    if (defer) defer->nslab = 0;
+    xcd_switch_once();
+    const WgradPlan w = wgrad_plan(Cg, Cy, R);
+    const GemmPlan g = gemm_plan(true, false, false, R, Co, Cg, false, false, Co);
+    GSAT_REQUIRE(G && W && OUT && Y && DW && ldg >= Cg && ldw >= Co && ldo >= Co && ldy >= Cy && lddw >= Cy, GSAT_ERR_ARG, "gemm_pair_x3: bad argument");
+    GSAT_REQUIRE(ldg % 4 == 0 && ldw % 4 == 0 && ldo % 4 == 0 && ldy % 4 == 0 && lddw % 4 == 0, GSAT_ERR_UNSUPPORTED,
+                 "gemm_pair_x3: leading dimensions must be multiples of 4");
+    GSAT_REQUIRE(((uintptr_t)G % 16 == 0) && ((uintptr_t)W % 16 == 0) && ((uintptr_t)OUT % 16 == 0) && ((uintptr_t)Y % 16 == 0) &&
+                 ((uintptr_t)DW % 16 == 0) && ((uintptr_t)ws % 16 == 0), GSAT_ERR_ARG, "gemm_pair_x3: operands, outputs and workspace must be 16-byte aligned");
+    GSAT_REQUIRE(ws && ws_floats >= w.ws_floats, GSAT_ERR_WORKSPACE, "gemm_pair_x3: workspace too small");
+    const int tiles = (int)ceil_div(R, WS_ROWS);
+    const unsigned chunks = (unsigned)ceil_div(Co, 256), dgx = (unsigned)pp.dgrad_blocks / chunks;
+    const unsigned both = (unsigned)std::min(pp.wgrad_blocks, pp.dgrad_blocks) / 8 * 8;
+    const PairWgrad wg{Y, ldy, ws, (int)Cy, w.rows, (unsigned)(Cy / WG_TILE), (unsigned)(Cg / WG_TILE), (unsigned)w.S};
+    const int out_flag = wsx3_out_flag(false, R, Co);
+    const unsigned blocks = (unsigned)(pp.wgrad_blocks + pp.dgrad_blocks);
+    int rc;
+#define PGO(S, Q) rc = pair_launch<S, Q>(stream, blocks, (size_t)pp.lds_bytes, G, ldg, W, ldw, OUT, ldo, (int)R, (int)Cg, (int)Co, g.nb, out_flag, tiles, dgx, both, wg)
+    if (g.kr == 8 && g.nq == 2) PGO(8, 2);            // Cg = 128: Co >= 256 | 128
+    else if (g.kr == 4 && g.nq == 2) PGO(4, 2);
+    else if (g.kr == 8 && g.nq == 4) PGO(8, 4);       // Cg = 256: Co = 128 | 64 | 32
+    else if (g.kr == 4 && g.nq == 4) PGO(4, 4);
+    else if (g.kr == 2 && g.nq == 4) PGO(2, 4);
+    else GSAT_REQUIRE(false, GSAT_ERR_UNSUPPORTED, "gemm_pair_x3: no kernel for KSTEPS = %d, NQ = %d", g.kr, g.nq);
+#undef PGO
+    if (rc) return rc;
+    const SlabJob job{ws, w.S, (size_t)Cg * Cy, (int)Cg, (int)Cy, lddw, accumulate ? 1 : 0, DW};
     if (defer) { *defer = job; return GSAT_OK; }
     return slab_reduce_jobs(stream, &job, 1);
 }
@@ -1368,6 +1508,22 @@ int gsat_gemm_wgrad_plan(int64_t Mo, int64_t No, int64_t K, int32_t* plan) {
 int gsat_gemm_wgrad_x3(int64_t Mo, int64_t No, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc,
                        int accumulate, float* workspace, size_t workspace_floats, void* stream) {
     return gemm_wgrad((hipStream_t)stream, Mo, No, K, A, lda, B, ldb, C, ldc, accumulate != 0, workspace, workspace_floats);
+}
+
+/* (paired, weight-gradient workgroups, backward-data workgroups, LDS bytes) of gsat_gemm_pair_x3 for these extents; see include/gsat_hip.h */
+int gsat_gemm_pair_plan(int64_t R, int64_t Cg, int64_t Co, int64_t Cy, int32_t* plan) {
+    GSAT_REQUIRE(plan && R > 0 && Cg > 0 && Co > 0 && Cy > 0, GSAT_ERR_ARG, "gsat_gemm_pair_plan: bad argument");
+    const PairPlan p = gemm_pair_plan(R, Cg, Co, Cy);
+    const int32_t v[4] = {p.paired, p.wgrad_blocks, p.dgrad_blocks, p.lds_bytes};
+    memcpy(plan, v, sizeof(v));
+    return GSAT_OK;
+}
+
+/* OUT[R,Co] = G W and DW[Cg,Cy] = (accumulate ? DW : 0) + G^T Y, the ordered slab sum included; see include/gsat_hip.h */
+int gsat_gemm_pair_x3(int64_t R, int64_t Cg, int64_t Co, int64_t Cy, const float* G, int64_t ldg, const float* W, int64_t ldw, float* OUT, int64_t ldo,
+                      const float* Y, int64_t ldy, float* DW, int64_t lddw, int accumulate, float* workspace, size_t workspace_floats, void* stream) {
+    GSAT_REQUIRE(R > 0 && Cg > 0 && Co > 0 && Cy > 0, GSAT_ERR_ARG, "gsat_gemm_pair_x3: bad argument");
+    return gemm_pair_x3((hipStream_t)stream, R, Cg, Co, Cy, G, ldg, W, ldw, OUT, ldo, Y, ldy, DW, lddw, accumulate != 0, workspace, workspace_floats);
 }
 
 /* the dispatch decisions of gsat_gemm_f32 (allow_split == 0) / gsat_gemm_bf16x3 for these arguments; see include/gsat_hip.h */

@@ -445,6 +445,22 @@ int gsat_gemm_bf16x3(int a_t, int b_t, int64_t M, int64_t N, int64_t K, const fl
 int gsat_gemm_wgrad_plan(int64_t Mo, int64_t No, int64_t K, int32_t* plan);
 int gsat_gemm_wgrad_x3(int64_t Mo, int64_t No, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                        float* C, int64_t ldc, int accumulate, float* workspace, size_t workspace_floats, void* stream);
+/*
+ * The two backward products of a Linear layer that read the same output gradient G [R,Cg] (R = rows of the batch), split-bf16 as above:
+ *   OUT[R,Co] = G W  (W [Cg,Co] row-major)          DW[Cg,Cy] = (accumulate ? DW : 0) + G^T Y  (Y [R,Cy] row-major)
+ * Where gsat_gemm_bf16x3(a_t = 0, b_t = 0) would take its weight-stationary kernel and gsat_gemm_wgrad_x3 its streaming kernel, and two
+ * workgroups' LDS fits a CU (Cg <= 256), both run in ONE launch: every workgroup runs one of the two kernels' bodies unchanged, the two kinds interleaved so that a CU holds one of each.
+ * OUT and DW have the bits of the two separate calls, which is what runs for every other shape and under GSAT_GEMM_PAIR=0.
+ * gsat_gemm_pair_plan (host arithmetic, no launch) writes HOST int32[4]:
+ *   [0] 1 = one launch, 0 = the two separate calls    [1] weight-gradient workgroups    [2] backward-data workgroups
+ *   [3] dynamic LDS bytes of a workgroup              ([1]..[3] are 0 when [0] is 0)
+ * The workspace is that of gsat_gemm_wgrad_x3(Cg, Cy, R) (gsat_gemm_wgrad_plan [3]), 16-byte aligned like G, W, OUT, Y and DW; every
+ * leading dimension a multiple of 4.
+ */
+int gsat_gemm_pair_plan(int64_t R, int64_t Cg, int64_t Co, int64_t Cy, int32_t* plan);
+int gsat_gemm_pair_x3(int64_t R, int64_t Cg, int64_t Co, int64_t Cy, const float* G, int64_t ldg, const float* W, int64_t ldw,
+                      float* OUT, int64_t ldo, const float* Y, int64_t ldy, float* DW, int64_t lddw, int accumulate,
+                      float* workspace, size_t workspace_floats, void* stream);
 
 /* =============================== attention extractor MLP ===================================== */
 
