@@ -23,6 +23,9 @@ from .explain import explanation_levels
 from .subgraph import (PaddedSubgraphBatch, SubgraphBatch, edge_subgraph, edge_subgraph_padded, explanation_fidelity, explanation_subgraph,
                        gather_rows, node_subgraph, node_subgraph_padded)
 from .subgraph import StackedExplanationBatch, explanation_fidelity_curve, explanation_stack
+from .subgraph import explanation_fidelity_curves, explanation_stack_multi
+from .explain import level_overlap
+from .replay import ReplayedDualFidelityCurve
 from .evaluate import (AttentionHistogram, EvaluationMeter, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve,
                        task_auroc_counts)
 from .eval_log import EpochLog, FidelityCurveLog, FidelityLog, delta_kl_segments
@@ -38,4 +41,5 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "ReplayedDualStep", "collate_padded_pair", "f1_sparsity_loss_valid", "EpochLog", "delta_kl_segments", "ReplayedEval",
            "ReplayedDualEval", "criterion_valid", "PaddedSubgraphBatch", "edge_subgraph_padded", "node_subgraph_padded", "FidelityLog", "ReplayedFidelity",
            "explanation_levels", "StackedExplanationBatch", "explanation_stack", "explanation_fidelity_curve", "FidelityCurveLog",
-           "ReplayedFidelityCurve"]
+           "ReplayedFidelityCurve", "explanation_stack_multi", "explanation_fidelity_curves", "level_overlap",
+           "ReplayedDualFidelityCurve"]

@@ -25,9 +25,12 @@ class PaddedBatch(Batch):
 
 
 def _take_padded(table, index):
-    """table[index] with zero rows where index is -1."""
+    """table[index] with zero rows where index is -1.  A table without rows (a batch without edges) gives zero rows only: there every
+    index is -1, and the clamped gather would read row 0 of nothing."""
     if table is None:
         return None
+    if int(table.shape[0]) == 0:
+        return table.new_zeros((int(index.shape[0]),) + tuple(table.shape[1:]))
     out = table.index_select(0, index.clamp(min=0))
     return out.masked_fill_((index < 0).view((-1,) + (1,) * (out.dim() - 1)), 0)
 

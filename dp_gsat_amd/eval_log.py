@@ -23,7 +23,7 @@ import torch
 
 from ._lib import GsatHipError, call, ptr, stream
 from .evaluate import MAX_BINS, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve
-from .explain import _att, _labels, attention_auroc, check_levels, delta_kl_stats, rank_edges_lds_cap
+from .explain import _att, _labels, attention_auroc, check_levels, check_rankings, delta_kl_stats, rank_edges_lds_cap
 from .graph_index import call_size, get_index
 
 FLAG_OVERFLOW, FLAG_FULL = 1, 2
@@ -276,12 +276,17 @@ class FidelityCurveLog:
     probability of the class predicted from the full batch (``p float64[max_graphs, V]``); ``state`` int64[20] = (graphs, batches, flags,
     real edges, kept edges of level 0 .. 15) lives on the device.  ``append`` is two kernel launches and reads nothing, so it replays inside
     a captured graph (``ReplayedFidelityCurve``).  An append that cannot be taken -- an overflowed batch or stack (flag bit 0), or one that
-    would exceed ``max_graphs`` (flag bit 1) -- writes nothing but its flag and is reported by ``compute``."""
+    would exceed ``max_graphs`` (flag bit 1) -- writes nothing but its flag and is reported by ``compute``.
 
-    def __init__(self, max_graphs: int, classes: int, ks=None, ratios=None, device=None):
+    ``rankings=R`` (``R * S`` at most 16): the log of a multi-ranking stack (``explanation_stack_multi``, ``V = 1 + 2 R S`` blocks).  The
+    same kernels run with ``R * S`` flat levels -- flat level ``r * S + s`` is ranking ``r``, level ``s`` -- and ``compute`` returns the
+    per-level entries as ``[R][S]`` nested lists under the same keys.  With ``rankings=1`` everything is as without it."""
+
+    def __init__(self, max_graphs: int, classes: int, ks=None, ratios=None, device=None, rankings: int = 1):
         ks, ratios = check_levels(ks, ratios)
         self.levels, self.by_ratio = tuple(ks if ks is not None else ratios), ratios is not None
-        S = len(self.levels)
+        self.rankings = check_rankings(rankings, len(self.levels))
+        S = self._flat = self.rankings * len(self.levels)
         self.variants = 2 * S + 1
         if int(max_graphs) < 0 or int(classes) < 1:
             raise ValueError("FidelityCurveLog needs a non-negative capacity and at least one logit column")
@@ -313,7 +318,7 @@ class FidelityCurveLog:
         for t, n in zip(words, (4 * self.variants, 4)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() < n or not t.is_cuda:
                 raise ValueError("valid words must be int32 ROCm tensors: (N_real, E_real, B, overflow), one row per variant for the stack")
-        call("gsat_fidelity_curve_append", ptr(z) if z.numel() else None, int(z.shape[0]) // self.variants, self.classes, len(self.levels),
+        call("gsat_fidelity_curve_append", ptr(z) if z.numel() else None, int(z.shape[0]) // self.variants, self.classes, self._flat,
              ptr(valid.contiguous()) if valid is not None else None, ptr(stack_valid.contiguous()), ptr(self.cls) if self.cls.numel() else None,
              ptr(self.p) if self.p.numel() else None, ptr(self.state), self.max_graphs, stream())
 
@@ -323,7 +328,7 @@ class FidelityCurveLog:
         the exact flip rates ``flip_plus = #(cls_drop != cls_full) / n`` and ``flip_minus = #(cls_keep != cls_full) / n`` and
         ``kept_fraction`` = kept edges / real edges (integer sums); ``p_full`` and ``n``.  fp64 sums in a fixed order: two runs over the same
         log are bitwise equal.  ValueError when an append was refused, or nothing was appended."""
-        S = len(self.levels)
+        S = self._flat
         call("gsat_fidelity_curve_reduce", ptr(self.cls) if self.cls.numel() else None, ptr(self.p) if self.p.numel() else None,
              ptr(self.state), self.max_graphs, S, ptr(self._out), stream())
         packed = self._out.cpu().numpy()                                                        # the one host read
@@ -339,8 +344,13 @@ class FidelityCurveLog:
         ints = packed[4:4 + 3 * S].reshape(3, S)
         sums = packed[4 + 3 * S:].view(np.float64)
         per_level = sums[1:].reshape(4, S)
-        return {"levels": list(self.levels),
-                "fidelity_plus": [float(v) / n for v in per_level[2]], "fidelity_minus": [float(v) / n for v in per_level[3]],
-                "p_full": float(sums[0]) / n, "p_keep": [float(v) / n for v in per_level[0]], "p_drop": [float(v) / n for v in per_level[1]],
-                "flip_plus": [int(v) / n for v in ints[1]], "flip_minus": [int(v) / n for v in ints[2]],
-                "kept_fraction": [int(v) / real_edges if real_edges else 0.0 for v in ints[0]], "n": n}
+        res = {"levels": list(self.levels),
+               "fidelity_plus": [float(v) / n for v in per_level[2]], "fidelity_minus": [float(v) / n for v in per_level[3]],
+               "p_full": float(sums[0]) / n, "p_keep": [float(v) / n for v in per_level[0]], "p_drop": [float(v) / n for v in per_level[1]],
+               "flip_plus": [int(v) / n for v in ints[1]], "flip_minus": [int(v) / n for v in ints[2]],
+               "kept_fraction": [int(v) / real_edges if real_edges else 0.0 for v in ints[0]], "n": n}
+        if self.rankings > 1:           # flat level r * S + s is ranking r, level s
+            per = len(self.levels)
+            for key in ("fidelity_plus", "fidelity_minus", "p_keep", "p_drop", "flip_plus", "flip_minus", "kept_fraction"):
+                res[key] = [res[key][r * per:(r + 1) * per] for r in range(self.rankings)]
+        return res

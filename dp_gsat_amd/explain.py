@@ -169,6 +169,56 @@ def check_levels(ks=None, ratios=None):
     return (levels, None) if ks is not None else (None, levels)
 
 
+def check_rankings(rankings, levels: int) -> int:
+    """The number of rankings a multi-ranking stack or log takes with ``levels`` levels each: ValueError unless it is a positive int and
+    ``rankings * levels`` is at most ``MAX_LEVELS`` (the stack lays ``1 + 2 * rankings * levels`` variants out)."""
+    if isinstance(rankings, bool) or int(rankings) != rankings or int(rankings) < 1:
+        raise ValueError("rankings must be a positive int")
+    if int(rankings) * int(levels) > MAX_LEVELS:
+        raise ValueError(f"rankings * levels must be at most {MAX_LEVELS}, got {int(rankings)} * {int(levels)}")
+    return int(rankings)
+
+
+def level_overlap(level_a, level_b, S: int, valid=None, out=None) -> torch.Tensor:
+    """Agreement of two rankings of the same edges (gsat_level_overlap): ADDS into ``out`` int64[S, 3] on the device -- a fresh zeroed
+    block when ``out`` is None -- per level ``s`` the counts ``#(a <= s & b <= s)``, ``#(a <= s)``, ``#(b <= s)`` over the edges that
+    are in some level at all, and returns it.  ``level_a`` / ``level_b``: uint8[E] from :func:`explanation_levels` with the same ``S``
+    levels; ``valid``: the int32[4] word of a padded batch -- entries at or beyond ``valid[1]`` are never loaded.  Integer and exact,
+    one launch (two with the zeroing), nothing read back: capturable.  Jaccard = ``c0 / (c1 + c2 - c0)``, overlap coefficient = ``c0 /
+    min(c1, c2)``."""
+    if isinstance(S, bool) or int(S) != S or not 1 <= int(S) <= MAX_LEVELS:
+        raise ValueError(f"level_overlap takes 1 to {MAX_LEVELS} levels")
+    S = int(S)
+    for t in (level_a, level_b):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+        if t.dtype != torch.uint8:
+            raise ValueError("levels must be uint8 tensors (explanation_levels)")
+    a, b = level_a.reshape(-1).contiguous(), level_b.reshape(-1).contiguous()
+    E = int(a.shape[0])
+    if int(b.shape[0]) != E:
+        raise ValueError(f"the two level vectors must have the same length, got {E} and {int(b.shape[0])}")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype != torch.int32 or valid.numel() < 4 or not valid.is_cuda:
+            raise ValueError("valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+        valid = valid.contiguous()
+    if out is None:
+        out = torch.empty((S, 3), dtype=torch.int64, device=a.device)
+        call("gsat_level_overlap_reset", ptr(out), S, stream())
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (S, 3) or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int64 ROCm tensor of shape [{S}, 3]")
+    call("gsat_level_overlap", ptr(a) if E else None, ptr(b) if E else None, E, S, ptr(valid) if valid is not None else None, ptr(out),
+         stream())
+    return out
+
+
+def level_overlap_reset(out: torch.Tensor) -> None:
+    """Zero an accumulator of :func:`level_overlap` by a kernel (no memset node, so a captured graph may hold it)."""
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or out.dim() != 2 or int(out.shape[1]) != 3 or not out.is_cuda:
+        raise ValueError("out must be an int64 ROCm tensor of shape [S, 3]")
+    call("gsat_level_overlap_reset", ptr(out), int(out.shape[0]), stream())
+
+
 def explanation_levels(att, edge_index, batch, ks=None, ratios=None, num_graphs: Optional[int] = None, *,
                        max_seg_edges: Optional[int] = None, ranked_graphs: Optional[int] = None) -> torch.Tensor:
     """uint8[E]: for every edge the smallest level ``s`` whose top-``ks[s]`` (or top-``ceil(ratios[s] * E_g)``) of its graph holds it,

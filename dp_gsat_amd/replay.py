@@ -24,7 +24,7 @@ from .graph_index import clear_cache, get_index, set_sync_free, sync_free
 from .gsat import get_r
 from .ops import edge_tensor
 from .padding import padded
-from .subgraph import edge_subgraph_padded, explanation_stack
+from .subgraph import edge_subgraph_padded, explanation_stack, explanation_stack_multi
 
 _MULTI_LABEL = "a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)"
 
@@ -966,6 +966,162 @@ class ReplayedFidelityCurve(_Replayed):
         fixed-count tail of fewer than ``batch_size`` graphs runs eagerly through the same code, and ``log.compute()`` -- one reduction
         launch, one host read -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
         return _run_epoch(self, graph_ids, epoch)
+
+    def overflowed(self) -> bool:
+        """True if a batch or a variant of its stack since the last call (or since capture) did not fit its capacity.  One host read;
+        clears the flag."""
+        return _take_overflow(self)
+
+
+class ReplayedDualFidelityCurve(_Replayed):
+    """``ReplayedDualFidelityCurve(dual_gsat, primal_ds, dual_ds, batch_size, ks=None, ratios=None, capacity=None, max_graphs=None,
+    seed=None, graphs=None, ragged=False)``: the fidelity curves of the TWO explanations a dual/primal model gives of the same primal edges
+    -- ranking 0: the primal edge attention, mixed with the dual one once ``epoch > mix_after_epoch``; ranking 1: the dual node attention
+    read on the primal edge slots (dual node row k is primal edge slot k) -- with their agreement, over ``S`` levels (``ks`` or
+    ``ratios``, ``2 S`` at most 16), as replays of captured hipGraphs.  Which of the two the classifier relies on, without edge labels.
+
+    One replay holds clear_cache; ``collate_padded_pair``; one gsat_seed_next from a private ``seed_state`` (the rules of
+    ``ReplayedDualEval``: ``run`` restarts it at ``(base, epoch << 32)``); ``dual_forward_pass(pb, db, epoch, False, dual_seed=word)``
+    under ``torch.no_grad()`` with every module in ``eval()`` mode; the fused ranking and gsat_fidelity_levels of both attentions on
+    the primal batch; ONE ``explanation_stack_multi`` -- the ``1 + 4 S`` variants around one copy of the batch --; ONE ``primal_clf``
+    forward WITHOUT ``edge_atten`` on the stack, as in ``ReplayedFidelityCurve``; ``log.append`` into a ``FidelityCurveLog(...,
+    rankings=2)``; and ``level_overlap`` of the two level rows into ``overlap`` int64[S, 3].  The mix is a host branch: TWO graphs
+    (unmixed, mixed), picked by ``epoch > mix_after_epoch``.  Nothing is read back per batch.
+
+    ``run(graph_ids, epoch)`` resets the log and the overlap block, replays every full batch -- ragged: every row of ``batches``, no eager
+    batch --, runs a fixed-count tail eagerly through the same code, and returns ``primal`` and ``dual`` (each the dict of
+    ``ReplayedFidelityCurve.run``), ``jaccard`` and ``overlap`` (lists over the levels: ``both / (a + b - both)`` and ``both / min(a,
+    b)`` of the kept edge sets, 0.0 where the denominator is 0), ``p_full`` and ``n``: one reduction launch and one host read, plus one
+    read of the overlap block.
+
+    After a step: ``edge_att`` and ``dual_att`` [E_cap, 1], ``edge_level`` uint8[2, E_cap], ``stack``, ``logits``, ``batch`` and
+    ``dual_batch``.  ``overflowed()`` / ``check_epoch`` as elsewhere.
+
+    The graphs write no parameter, buffer or optimizer state and draw from neither the device seed stream nor torch's generators: a curve
+    epoch between ``ReplayedDualStep`` steps leaves the training run bitwise unchanged.
+
+    Refused with ValueError before anything is captured: bad levels or ``2 * S > 16``; what a padded pair refuses (edge attention, the
+    multi-label criterion, ``check_pair``, a capacity that is no triple); ``sync_group`` BatchNorm; a model without ``dual_forward_pass``;
+    a primal dataset without graph labels or without ``edge_label`` (the f1 term of ``dual_forward_pass`` needs it); a largest primal
+    graph above ``rank_edges_lds_cap()``."""
+
+    def __init__(self, dual_gsat, primal_ds, dual_ds, batch_size: int, ks=None, ratios=None, capacity: Optional[tuple] = None,
+                 max_graphs: Optional[int] = None, seed: Optional[int] = None, graphs=None, ragged: bool = False):
+        self.ks, self.ratios = _explain.check_levels(ks, ratios)
+        self.levels = tuple(self.ks if self.ks is not None else self.ratios)
+        _explain.check_rankings(2, len(self.levels))
+        m = dual_gsat
+        if not hasattr(m, "dual_forward_pass"):
+            raise ValueError("ReplayedDualFidelityCurve replays DualGSAT.dual_forward_pass; ReplayedFidelityCurve covers a plain GSAT")
+        _refuse_sync_group(m)
+        if primal_ds.y_all is None or dual_ds.y_all is None or primal_ds.edge_label_all is None:
+            raise ValueError("ReplayedDualFidelityCurve needs datasets with graph labels and a primal dataset with edge_label (the f1 "
+                             "term of dual_forward_pass takes it)")
+        self.max_seg_edges = int(primal_ds.edge_counts.max()) if primal_ds.num_graphs else 0          # one host read, here
+        if self.max_seg_edges > _explain.rank_edges_lds_cap():
+            raise ValueError(f"the primal dataset's largest graph has {self.max_seg_edges} edges, above rank_edges_lds_cap() = "
+                             f"{_explain.rank_edges_lds_cap()}: the captured ranking takes the fused path only")
+        _padded_pair_setup(self, m, primal_ds, dual_ds, batch_size, capacity, graphs, ragged)
+        dev = primal_ds.x_all.device
+        if seed is None:        # the mix of ReplayedDualEval: follows torch.manual_seed, draws nothing
+            seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & 0x7FFFFFFFFFFFFFFF
+        self.base = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.seed_state = torch.empty(2, dtype=torch.int64, device=dev)
+        _EVAL_SEED_STATES.append(self.seed_state)
+        self._set_seed_state(0)
+        self._max_graphs = primal_ds.num_graphs if max_graphs is None else int(max_graphs)
+        self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.overlap = torch.zeros((len(self.levels), 3), dtype=torch.int64, device=dev)
+        self.log = self.batch = self.dual_batch = self.edge_att = self.dual_att = self.edge_level = self.stack = self.logits = None
+        try:
+            with _capture_mode(m, evaluating=True):
+                self._warm_up_and_capture(self._make_log, self._reset)
+        finally:
+            self._reset()
+            self._set_seed_state(0)
+            self._overflow.zero_()
+
+    _set_seed_state = ReplayedDualEval._set_seed_state
+
+    def _reset(self):
+        if self.log is not None:
+            self.log.reset()
+        _explain.level_overlap_reset(self.overlap)
+
+    def _make_log(self):
+        pb, _ = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity, ragged=self.ragged)
+        with torch.no_grad(), padded(pb.valid, pb.capacity):
+            get_index(pb.edge_index, int(pb.x.shape[0])).graphs(pb.batch, int(pb.num_graphs))
+            logits = self.model.primal_clf(pb.x, pb.edge_index, pb.batch, getattr(pb, "edge_attr", None))
+        self.log = FidelityCurveLog(self._max_graphs, int(logits.shape[1]), self.ks, self.ratios, self.primal_ds.x_all.device, rankings=2)
+
+    def _forward(self, pb, db, epoch):
+        """The pair's eval-mode forward with the stream's next seed word, both rankings, the stack, the one backbone forward, the append
+        and the overlap for the pair ``pb, db`` -- padded (the captured body) or ``collate`` output (the eager tail, stacked at the captured
+        batch size); the modules are in eval mode and sync_loss_dict is off."""
+        m = self.model
+        word = None
+        if m.gumbel_noise_in_eval:
+            word = torch.empty(1, dtype=torch.int64, device=self.seed_state.device)
+            call("gsat_seed_next", ptr(self.seed_state), ptr(word), stream())
+        kept = m.keep_dual_att
+        m.keep_dual_att = True
+        try:
+            with torch.no_grad():
+                att = edge_tensor(m.dual_forward_pass(pb, db, epoch, False, dual_seed=word)[0]).detach()
+                dual_att = m.dual_att[:att.shape[0]]
+                stack, logits = self._score(pb, att, dual_att)
+        finally:
+            m.keep_dual_att, m.dual_att = kept, None
+        return att, dual_att, stack, logits, word
+
+    def _score(self, pb, att, dual_att):
+        """Both rankings of the primal batch ``pb`` in one stack, the one backbone forward, the append and the overlap."""
+        valid = getattr(pb, "valid", None)
+        stack = explanation_stack_multi(pb, [att, dual_att], ks=self.ks, ratios=self.ratios, batch_size=self.batch_size,
+                                        max_seg_edges=self.max_seg_edges)
+        logits = self.model.primal_clf(stack.x, stack.edge_index, stack.batch, stack.edge_attr)
+        over = stack.valid[:, 3].amax().view(1)
+        self._overflow.bitwise_or_(over if valid is None else over | valid[3:4])
+        self.log.append(logits, stack.valid, valid)
+        _explain.level_overlap(stack.edge_level[0], stack.edge_level[1], len(self.levels), valid=valid, out=self.overlap)
+        return stack, logits
+
+    def run_once(self, mixed: bool):
+        """The body of one captured graph, run on the current stream."""
+        clear_cache()
+        pb, db = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity, ragged=self.ragged)
+        db.r = self.r
+        att, dual_att, stack, logits, word = self._forward(pb, db, _mix_epoch(self.model, mixed))
+        self._publish(mixed, batch=pb, dual_batch=db, edge_att=att, dual_att=dual_att, edge_level=stack.edge_level, stack=stack,
+                      logits=logits, _word=word)
+
+    def run(self, graph_ids, epoch: int) -> dict:
+        """One curve epoch over ``graph_ids`` (any number, in visiting order) at ``epoch``: the seed stream restarts at (base, epoch << 32),
+        the log and the overlap block are reset, every full batch is a replay of the graph ``epoch > mix_after_epoch`` picks, a tail of
+        fewer than ``batch_size`` graphs runs eagerly through the same code on both datasets' ``collate``, and ``log.compute()`` -- one
+        reduction launch, one host read -- plus one read of ``overlap`` give the result.  Ragged: the ids are packed by ``batches`` and
+        every batch is a replay."""
+        self._set_seed_state(int(epoch) << 32)
+        ids = torch.as_tensor(graph_ids).reshape(-1)
+        B, n = self.batch_size, int(ids.numel())
+        self._reset()
+        rows, left = (self.batches(ids), 0) if self.ragged else ([ids[s:s + B] for s in range(0, n - B + 1, B)], n % B)
+        for row in rows:
+            self.step(row, epoch)
+        if left:
+            with _forward_mode(self.model, True):
+                tail = ids[n - left:].to(self.graph_ids.device, torch.int64)
+                self._forward(*[ds.collate(tail) for ds in self._datasets], epoch)
+        res = self.log.compute()
+        counts = self.overlap.tolist()                                                          # the read of the overlap block
+        per_level = ("fidelity_plus", "fidelity_minus", "p_keep", "p_drop", "flip_plus", "flip_minus", "kept_fraction")
+        out = {name: dict({key: res[key][r] for key in per_level}, levels=res["levels"], p_full=res["p_full"], n=res["n"])
+               for r, name in enumerate(("primal", "dual"))}
+        out["jaccard"] = [c[0] / (c[1] + c[2] - c[0]) if c[1] + c[2] - c[0] else 0.0 for c in counts]
+        out["overlap"] = [c[0] / min(c[1], c[2]) if min(c[1], c[2]) else 0.0 for c in counts]
+        out["p_full"], out["n"] = res["p_full"], res["n"]
+        return out
 
     def overflowed(self) -> bool:
         """True if a batch or a variant of its stack since the last call (or since capture) did not fit its capacity.  One host read;

@@ -359,7 +359,8 @@ class StackedExplanationBatch(Batch):
     every variant), ``levels`` (the ``ks`` or ``ratios``) and ``by_ratio``, ``variants`` (``2 * len(levels) + 1``), ``segment_offsets``
     (host ints: variant ``v`` owns the edge slots ``[segment_offsets[v], segment_offsets[v + 1])``), ``node_capacity`` (variant ``v`` owns
     the node rows ``[v * node_capacity, (v + 1) * node_capacity)``), ``graphs_per_variant`` (the padding graph last), ``edge_id``
-    (int64[E_stack]: the input's edge slot, -1 for padding) and ``edge_level`` (uint8[E]: :func:`explanation_levels` of the input)."""
+    (int64[E_stack]: the input's edge slot, -1 for padding) and ``edge_level`` (uint8[E]: :func:`explanation_levels` of the input).
+    ``rankings`` is 1; of :func:`explanation_stack_multi` it is ``R``, with ``variants = 1 + 2 R S`` and ``edge_level`` uint8[R, E]."""
 
     def check(self) -> "StackedExplanationBatch":
         """One host read of ``valid``: raises ValueError when a variant overflowed (it is then all padding)."""
@@ -388,19 +389,51 @@ def explanation_stack(data, att, ks=None, ratios=None, batch_size: Optional[int]
     and the stack's batch index, whatever ``S`` is, and nothing read back: capturable.  A
     variant that does not fit, an overflowed input or a bad node id is all padding with ``valid == (0, 0, 0, 1)``: a ValueError after one
     host read of ``valid`` -- in sync-free mode or under capture nothing is read and ``.check()`` reports it."""
-    from .explain import check_levels, explanation_levels
+    return _explanation_stack(data, [att], ks, ratios, batch_size, max_seg_edges, None if edge_level is None else [edge_level], False)
+
+
+def explanation_stack_multi(data, atts, ks=None, ratios=None, batch_size: Optional[int] = None, *, max_seg_edges: Optional[int] = None,
+                            edge_levels=None) -> StackedExplanationBatch:
+    """:func:`explanation_stack` for ``R`` explanations ``atts`` of the same edges around ONE copy of the batch itself
+    (gsat_fidelity_stack_multi): ``V = 1 + 2 R S`` variants -- ``v = 0`` the batch, ``v = 1 + r S + s`` "ranking r, level s alone", ``v = 1
+    + R S + r S + s`` "the batch without it" -- so that ONE backbone forward scores ``R`` fidelity curves, and a ``FidelityCurveLog(...,
+    rankings=R)`` takes its logits as they are.  Every variant of ranking ``r`` holds, bit for bit, what ``explanation_stack(data,
+    atts[r], ...)`` holds for it, moved to its new node rows and graph ids; the segment capacities are those of ``explanation_stack``,
+    ranking after ranking.  ``atts``: a sequence of ``R`` attentions; ``edge_levels``: in their place, levels computed before -- a
+    sequence of ``R`` uint8[E] tensors or one uint8[R, E].  The result has ``rankings = R``, ``variants`` and ``edge_level`` uint8[R, E].
+    Still four launches for the stack whatever ``R`` and ``S`` are, nothing read back: capturable with ``max_seg_edges``.  Refused like
+    ``explanation_stack``, and when ``R * S`` is above 16."""
+    if edge_levels is None:
+        if atts is None or isinstance(atts, torch.Tensor) or len(atts) < 1:
+            raise ValueError("atts must be a sequence of one or more attentions (one tensor: explanation_stack)")
+        atts = list(atts)
+    else:
+        edge_levels = list(edge_levels) if not isinstance(edge_levels, torch.Tensor) else (
+            list(edge_levels) if edge_levels.dim() == 2 else [edge_levels])
+        if len(edge_levels) < 1:
+            raise ValueError("edge_levels must hold one or more level rows")
+        atts = [None] * len(edge_levels)
+    return _explanation_stack(data, atts, ks, ratios, batch_size, max_seg_edges, edge_levels, True)
+
+
+def _explanation_stack(data, atts, ks, ratios, batch_size, max_seg_edges, edge_levels, multi) -> StackedExplanationBatch:
+    """The body of :func:`explanation_stack` (``multi`` False: one ranking through gsat_fidelity_stack, ``edge_level`` uint8[E]) and
+    :func:`explanation_stack_multi` (gsat_fidelity_stack_multi, ``edge_level`` uint8[R, E])."""
+    from .explain import check_levels, check_rankings, explanation_levels
     from .replay import keep_capacity
     ks, ratios = check_levels(ks, ratios)
     levels = ks if ks is not None else ratios
-    S = len(levels)
-    V = 2 * S + 1
+    S, R = len(levels), len(atts)
+    if multi:
+        check_rankings(R, S)
+    V = 2 * R * S + 1
     x, edge_index, batch = data.x, data.edge_index, data.batch
     if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
         raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
     N, E, dev = int(x.shape[0]), int(edge_index.shape[1]), edge_index.device
     if batch.dtype != torch.int64 or batch.dim() != 1 or int(batch.shape[0]) != N:
         raise ValueError("batch must be an int64 vector with one entry per node")
-    _need_cuda(x, edge_index, batch, edge_level)
+    _need_cuda(x, edge_index, batch, *(edge_levels or ()))
     capturing = torch.cuda.is_current_stream_capturing()
     valid_in = getattr(data, "valid", None)
     if valid_in is not None:
@@ -421,29 +454,41 @@ def explanation_stack(data, att, ks=None, ratios=None, batch_size: Optional[int]
         Gp, N_cap = real + 1, N + 2
     B = real if batch_size is None else int(batch_size)
     ei, batch = edge_index.contiguous(), batch.contiguous()
-    if edge_level is None:
-        a = ops.edge_tensor(att)
-        if not isinstance(a, torch.Tensor) or a.numel() != E:
-            raise ValueError(f"attention must have one entry for each of the {E} edges")
-        edge_level = explanation_levels(a, ei, batch, ks=ks, ratios=ratios, num_graphs=Gp if valid_in is not None else real,
-                                        max_seg_edges=max_seg_edges, ranked_graphs=real if max_seg_edges is not None else None)
-    elif edge_level.dtype != torch.uint8 or edge_level.numel() != E:
-        raise ValueError(f"edge_level must be a uint8 tensor with one entry for each of the {E} edges")
-    edge_level = edge_level.reshape(-1).contiguous()
-    caps = [E] + [keep_capacity(E, B, **({"k": l} if ks is not None else {"ratio": l})) for l in levels] + [E] * S
+    rows = []
+    for r in range(R):
+        if edge_levels is None:
+            a = ops.edge_tensor(atts[r])
+            if not isinstance(a, torch.Tensor) or a.numel() != E:
+                raise ValueError(f"attention must have one entry for each of the {E} edges")
+            rows.append(explanation_levels(a, ei, batch, ks=ks, ratios=ratios, num_graphs=Gp if valid_in is not None else real,
+                                           max_seg_edges=max_seg_edges, ranked_graphs=real if max_seg_edges is not None else None))
+        else:
+            lv = edge_levels[r]
+            if not isinstance(lv, torch.Tensor) or lv.dtype != torch.uint8 or lv.numel() != E:
+                raise ValueError(f"edge_level must be a uint8 tensor with one entry for each of the {E} edges")
+            rows.append(lv.reshape(-1).contiguous())
+    edge_level = torch.stack(rows) if multi else rows[0]
+    keep_caps = [keep_capacity(E, B, **({"k": l} if ks is not None else {"ratio": l})) for l in levels]
+    caps = [E] + keep_caps * R + [E] * (R * S)
     offsets = [0]
     for c in caps:
         offsets.append(offsets[-1] + int(c))
     E_stack = offsets[-1]
-    ws_bytes = max(call_size("gsat_fidelity_stack_workspace_bytes", E, S), 256)
+    ws_bytes = max(call_size("gsat_fidelity_stack_multi_workspace_bytes", E, R, S) if multi
+                   else call_size("gsat_fidelity_stack_workspace_bytes", E, S), 256)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     new_ei = torch.empty(2, E_stack, dtype=torch.int64, device=dev)
     edge_id = torch.empty(E_stack, dtype=torch.int64, device=dev)
     new_batch = torch.empty(V * N_cap, dtype=torch.int64, device=dev)
     valid = torch.empty(V, 4, dtype=torch.int32, device=dev)
     some = lambda t: ptr(t) if t is not None and t.numel() else None
-    call("gsat_fidelity_stack", some(ei), E, N, some(batch), real, ptr(valid_in) if valid_in is not None else None, some(edge_level), S, Gp,
-         N_cap, (ctypes.c_int64 * (V + 1))(*offsets), some(new_ei), some(edge_id), ptr(new_batch), ptr(valid), ptr(ws), ws_bytes, stream())
+    head = (some(ei), E, N, some(batch), real, ptr(valid_in) if valid_in is not None else None, some(edge_level))
+    tail = (Gp, N_cap, (ctypes.c_int64 * (V + 1))(*offsets), some(new_ei), some(edge_id), ptr(new_batch), ptr(valid), ptr(ws), ws_bytes,
+            stream())
+    if multi:
+        call("gsat_fidelity_stack_multi", *head, R, S, *tail)
+    else:
+        call("gsat_fidelity_stack", *head, S, *tail)
     if not (sync_free() or capturing) and int(valid[:, 3].any()):                                   # the one host read
         raise ValueError(_overflow_text((N_cap, tuple(caps))))
     if N_cap != N:
@@ -457,7 +502,7 @@ def explanation_stack(data, att, ks=None, ratios=None, batch_size: Optional[int]
     stack = StackedExplanationBatch(x=x.repeat((V,) + (1,) * (x.dim() - 1)), edge_index=new_ei, batch=new_batch, edge_attr=edge_attr,
                                     y=getattr(data, "y", None), num_graphs=V * Gp, valid=valid, levels=tuple(levels),
                                     by_ratio=ratios is not None, variants=V, segment_offsets=tuple(offsets), node_capacity=N_cap,
-                                    graphs_per_variant=Gp, edge_id=edge_id, edge_level=edge_level)
+                                    graphs_per_variant=Gp, edge_id=edge_id, edge_level=edge_level, rankings=R)
     # a backbone forward on the stack then returns num_graphs rows and never reads batch.max() back
     get_index(new_ei, V * N_cap).graphs(new_batch, V * Gp)
     return stack
@@ -492,3 +537,46 @@ def explanation_fidelity_curve(clf, data, att, ks=None, ratios=None) -> dict:
     return {"levels": stack.levels, "fidelity_plus": mean(p[0] - p[1 + S:]), "fidelity_minus": mean(p[0] - p[1:1 + S]), "p_full": mean(p[0]),
             "p_keep": mean(p[1:1 + S]), "p_drop": mean(p[1 + S:]), "flip_plus": flips[1 + S:], "flip_minus": flips[1:1 + S],
             "kept_fraction": kept[1:1 + S] / kept[0], "n": n, "logits": logits}
+
+
+def explanation_fidelity_curves(clf, data, atts, ks=None, ratios=None, *, batch_size: Optional[int] = None,
+                                max_seg_edges: Optional[int] = None) -> dict:
+    """:func:`explanation_fidelity_curve` for ``R`` explanations ``atts`` of the same edges at once: eval mode, no grad,
+    :func:`explanation_stack_multi`, ONE ``clf`` forward WITHOUT ``edge_atten`` on the ``1 + 2 R S`` variants.  The same dict with a
+    leading ranking axis -- ``fidelity_plus`` / ``fidelity_minus`` / ``p_keep`` / ``p_drop`` / ``flip_plus`` / ``flip_minus`` /
+    ``kept_fraction`` of shape [R, S], ``p_full`` and ``n`` 0-dim, ``levels``, the stacked ``logits [V, graphs_per_variant, C]`` -- plus,
+    for ``R == 2``, ``jaccard`` and ``overlap`` [S]: :func:`~dp_gsat_amd.explain.level_overlap` of the two rankings' levels, as
+    ``both / (a + b - both)`` and ``both / min(a, b)`` (0 where the denominator is 0)."""
+    from .explain import level_overlap
+    was_training = clf.training
+    clf.eval()
+    try:
+        with torch.no_grad():
+            stack = explanation_stack_multi(data, atts, ks=ks, ratios=ratios, batch_size=batch_size, max_seg_edges=max_seg_edges)
+            R, S, V, Gp = stack.rankings, len(stack.levels), stack.variants, stack.graphs_per_variant
+            logits = clf(stack.x, stack.edge_index, stack.batch, stack.edge_attr).view(V, Gp, -1)
+            z = logits.double()
+            real = (torch.arange(Gp, device=z.device) < stack.valid[0, 2]).double()          # the padding graph and empty slots count 0
+            n = real.sum()
+            if z.shape[2] > 1:
+                cls = z.argmax(dim=2)
+                p = torch.softmax(z, dim=2).gather(2, cls[0].expand(V, Gp).unsqueeze(2)).squeeze(2)
+            else:
+                cls = (z[:, :, 0] >= 0).long()
+                p = torch.sigmoid(torch.where(cls[0] != 0, 1.0, -1.0) * z[:, :, 0])
+            mean = lambda t: (t * real).sum(dim=-1) / n
+            flips = mean((cls != cls[0]).double())
+            kept = stack.valid[:, 1].double()
+            keep, drop = slice(1, 1 + R * S), slice(1 + R * S, V)
+            out = {"levels": stack.levels, "fidelity_plus": mean(p[0] - p[drop]).view(R, S), "fidelity_minus": mean(p[0] - p[keep]).view(R, S),
+                   "p_full": mean(p[0]), "p_keep": mean(p[keep]).view(R, S), "p_drop": mean(p[drop]).view(R, S),
+                   "flip_plus": flips[drop].view(R, S), "flip_minus": flips[keep].view(R, S), "kept_fraction": (kept[keep] / kept[0]).view(R, S),
+                   "n": n, "logits": logits}
+            if R == 2:
+                c = level_overlap(stack.edge_level[0], stack.edge_level[1], S, valid=getattr(data, "valid", None)).double()
+                union, least = c[:, 1] + c[:, 2] - c[:, 0], torch.minimum(c[:, 1], c[:, 2])
+                out["jaccard"] = torch.where(union > 0, c[:, 0] / union.clamp(min=1.0), torch.zeros_like(union))
+                out["overlap"] = torch.where(least > 0, c[:, 0] / least.clamp(min=1.0), torch.zeros_like(least))
+    finally:
+        clf.train(was_training)
+    return out

@@ -1072,6 +1072,45 @@ int gsat_fidelity_curve_reduce(const int32_t* log_cls, const double* log_p, cons
 /* log_state int64[20] = 0, by a kernel (no memset node). */
 int gsat_fidelity_curve_reset(int64_t* log_state, void* stream);
 
+/*
+ * gsat_fidelity_stack for `rankings` explanations of the same edges around ONE full variant: level uint8[rankings, E], row r being what
+ * gsat_fidelity_levels writes for ranking r with the same `levels`.  rankings, levels >= 1 and rankings * levels <= 16 (GSAT_ERR_ARG
+ * otherwise).  With R = rankings and S = levels there are V = 1 + 2 R S variants:
+ *   v = 0                      the batch itself
+ *   v = 1 + r S + s            the edges with level[r][e] <= s
+ *   v = 1 + R S + r S + s      the edges with level[r][e] > s
+ * so gsat_fidelity_curve_append / _reduce called with levels = R S hold ranking r, level s at their flat level r S + s.  Every other
+ * argument, the guards, the overflow rule and the outputs are gsat_fidelity_stack's with this V: segment_offsets int64[V + 1] in HOST
+ * memory, valid_out int32[V, 4], out_batch int64[V * cap_nodes].  The segment of a variant of ranking r holds, bit for bit, what
+ * gsat_fidelity_stack writes for level row r alone at the same segment length and cap_nodes; only the node-id and graph-id offsets
+ * follow the new variant index.  An overflowing variant is all padding alone; valid_in[3] or a node id out of range makes every variant
+ * all padding.  4 launches whatever R and S are (per-workgroup counts over the R (S + 1) bins, one scan workgroup, scatter, fill), no
+ * atomics, nothing read back: capturable and bitwise repeatable.  A thread loads the endpoints of its edge slots once and each of
+ * their R level bytes once.  workspace: gsat_fidelity_stack_multi_workspace_bytes(E, rankings, levels) (0 for arguments out of range).
+ * replaces: R calls of gsat_fidelity_stack and R stacked backbone forwards (each with its own copy of the batch) by one.
+ */
+size_t gsat_fidelity_stack_multi_workspace_bytes(int64_t E, int64_t rankings, int64_t levels);
+int gsat_fidelity_stack_multi(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* batch, int64_t G, const int32_t* valid_in,
+                              const uint8_t* level, int64_t rankings, int64_t levels, int64_t graphs_per_variant, int64_t cap_nodes,
+                              const int64_t* segment_offsets, int64_t* out_edge_index, int64_t* out_edge_id, int64_t* out_batch,
+                              int32_t* valid_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Agreement of two rankings of the same edges, level by level.  level_a, level_b uint8[E] (gsat_fidelity_levels with the same
+ * `levels`, 1 .. 16); valid int32[4] (nullable): the first clamp(valid[1], 0, E) entries count -- none when valid[3] is set -- and the
+ * others are never loaded; without it all E.  ADDS into acc int64[levels, 3], per level s:
+ *   acc[s][0] += #(a <= s and b <= s)    acc[s][1] += #(a <= s)    acc[s][2] += #(b <= s)
+ * An entry whose level is `levels` or above (in no level: the padding graph, or below every cut) is in none of the counts.  One
+ * launch: per-workgroup LDS counts, then one int64 atomicAdd per bin and workgroup -- integer sums, so the result does not depend on
+ * the order and is repeatable.  Capturable.  Jaccard of level s = acc[s][0] / (acc[s][1] + acc[s][2] - acc[s][0]), overlap
+ * coefficient = acc[s][0] / min(acc[s][1], acc[s][2]).  E < 2^31 (GSAT_ERR_UNSUPPORTED otherwise).
+ */
+int gsat_level_overlap(const uint8_t* level_a, const uint8_t* level_b, int64_t E, int64_t levels, const int32_t* valid, int64_t* acc,
+                       void* stream);
+
+/* acc int64[levels, 3] = 0, by a kernel (no memset node). */
+int gsat_level_overlap_reset(int64_t* acc, int64_t levels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
