@@ -26,7 +26,7 @@ from .subgraph import StackedExplanationBatch, explanation_fidelity_curve, expla
 from .subgraph import explanation_fidelity_curves, explanation_stack_multi
 from .explain import level_overlap
 from .replay import ReplayedDualFidelityCurve
-from .evaluate import (AttentionHistogram, EvaluationMeter, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve,
+from .evaluate import (AttentionHistogram, EvaluationMeter, attention_histogram, classifier_accuracy, classifier_rocauc, classifier_rocauc_tasks, pr_curve,
                        task_auroc_counts)
 from .eval_log import EpochLog, FidelityCurveLog, FidelityLog, delta_kl_segments
 
@@ -36,7 +36,7 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "process_data", "reorder_like", "set_seed", "DualGSAT", "f1_sparsity_loss", "LEConv", "SPMotifNet", "PackedDataset", "line_graph", "line_graph_undirected",
            "EdgeRanking", "ExplanationMeter", "attention_auroc", "delta_kl", "precision_at_k", "rank_edges", "topk_edge_mask",
            "SubgraphBatch", "edge_subgraph", "node_subgraph", "explanation_subgraph", "explanation_fidelity", "gather_rows",
-           "AttentionHistogram", "EvaluationMeter", "attention_histogram", "classifier_accuracy", "classifier_rocauc", "pr_curve",
+           "AttentionHistogram", "EvaluationMeter", "attention_histogram", "classifier_accuracy", "classifier_rocauc", "classifier_rocauc_tasks", "pr_curve",
            "task_auroc_counts", "PaddedBatch", "padded", "current_padding", "ReplayedStep",
            "ReplayedDualStep", "collate_padded_pair", "f1_sparsity_loss_valid", "EpochLog", "delta_kl_segments", "ReplayedEval",
            "ReplayedDualEval", "criterion_valid", "PaddedSubgraphBatch", "edge_subgraph_padded", "node_subgraph_padded", "FidelityLog", "ReplayedFidelity",

@@ -146,6 +146,8 @@ SIGNATURES = {
     "gsat_fidelity_curve_append": (INT, [P, I64, I64, I64, P, P, P, P, P, I64, P]),
     "gsat_fidelity_curve_reduce": (INT, [P, P, P, I64, I64, P, P]),
     "gsat_fidelity_curve_reset": (INT, [P, P]),
+    "gsat_fidelity_curve_append_tasks": (INT, [P, I64, I64, I64, P, P, P, P, P, I64, P]),
+    "gsat_fidelity_curve_reduce_tasks": (INT, [P, P, P, I64, I64, I64, P, P]),
     "gsat_fidelity_stack_multi_workspace_bytes": (SZ, [I64, I64, I64]),
     "gsat_fidelity_stack_multi": (INT, [P, I64, I64, P, I64, P, P, I64, I64, I64, I64, P, P, P, P, P, P, SZ, P]),
     "gsat_level_overlap": (INT, [P, P, I64, I64, P, P, P]),

@@ -8,6 +8,7 @@
 //                          repeatable), packed with the counters for ONE host read.
 //   gsat_fidelity_reset  : zeroes the counters with a kernel (no memset node).
 //   gsat_fidelity_curve_append / _reduce / _reset : the same log with a level axis, for the logits of a stacked batch (fidelity_stack.hip).
+//   gsat_fidelity_curve_append_tasks / _reduce_tasks : the curve log of a multi-label head, one binary decision per (graph, task).
 #include "common.h"
 #include <algorithm>
 
@@ -219,6 +220,76 @@ k_fidc_reduce(const int32_t* __restrict__ log_cls, const double* __restrict__ lo
     }
 }
 
+// ---- the curve log with a task axis (FidelityCurveLog(..., tasks=T)) ------------------------------------------------------------------------
+// A multi-label head: every (graph, task) is a binary decision of its own -- class z >= 0, probability sigmoid(+-z), the one-logit rules of
+// fid_class / fid_prob.  logits fp32[V * Gp, T]; log_cls / log_p [max_graphs, T, V].  The state words and the plan are fidc_plan's, and the
+// commit is k_fidc_commit itself: state[0] counts graphs.
+
+// one thread per (graph, task) below the count, the task running fastest: a wavefront reads consecutive floats of one block's rows, V times
+__global__ void __launch_bounds__(FID_BLOCK)
+k_fidt_rows(const float* __restrict__ logits, int64_t Gp, int T, int V, const int32_t* __restrict__ valid, const int32_t* __restrict__ stack_valid,
+            int32_t* __restrict__ log_cls, double* __restrict__ log_p, const int64_t* __restrict__ state, int64_t max_graphs) {
+    const FidPlan p = fidc_plan(valid, stack_valid, V, Gp, state, max_graphs);
+    if (p.flag) return;
+    const int64_t stride = (int64_t)gridDim.x * FID_BLOCK, items = p.g * T;
+    for (int64_t t = (int64_t)blockIdx.x * FID_BLOCK + threadIdx.x; t < items; t += stride) {   // t = i * T + task
+        const int cls = fid_class(logits + t, 1);
+        int32_t* oc = log_cls + (p.g0 * T + t) * V;
+        double* op = log_p + (p.g0 * T + t) * V;
+        for (int v = 0; v < V; ++v) {
+            const float* zv = logits + (int64_t)v * Gp * T + t;
+            oc[v] = v == 0 ? cls : fid_class(zv, 1);
+            op[v] = fid_prob(zv, 1, cls);
+        }
+    }
+}
+
+// Workgroup t reduces task t: thread k adds graphs k, k + 256, ... in that order, level after level (the order of k_fidc_reduce, whose sums
+// it therefore repeats bit for bit at T = 1).  out int64[4 + S + T (1 + 6 S)]:
+//   [0, 4)                         graphs, batches, flags, real edges                      (workgroup 0)
+//   [4, 4 + S)                     kept edges per level                                    (workgroup 0)
+//   then, with A = 4 + S:  A + (0 T + t) S + s   #(cls_drop_s != cls_full) of task t
+//                          A + (1 T + t) S + s   #(cls_keep_s != cls_full) of task t
+//   then the bits of doubles, with D = A + 2 T S:  D + t   the sum of p_full of task t
+//                          D + T + (k T + t) S + s   k = 0 .. 3: the sums of p_keep_s, p_drop_s, p_full - p_drop_s, p_full - p_keep_s
+__global__ void __launch_bounds__(FID_BLOCK)
+k_fidt_reduce(const int32_t* __restrict__ log_cls, const double* __restrict__ log_p, const int64_t* __restrict__ state, int64_t max_graphs, int S,
+              int T, int64_t* __restrict__ out) {
+    __shared__ double sh[FID_BLOCK / 64];
+    const int V = 2 * S + 1, task = blockIdx.x;
+    const int64_t n = min<int64_t>(max<int64_t>(state[0], 0), max_graphs);
+    const int64_t A = 4 + S, D = A + 2 * (int64_t)T * S;
+    double full = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += FID_BLOCK) full += log_p[(i * T + task) * V];
+    full = fid_block_sum(full, sh);
+    if (threadIdx.x == 0) {
+        if (task == 0) {
+            for (int k = 0; k < 4; ++k) out[k] = state[k];
+            for (int s = 0; s < S; ++s) out[4 + s] = state[4 + s];
+        }
+        out[D + task] = __double_as_longlong(full);
+    }
+    for (int s = 0; s < S; ++s) {
+        double a[4] = {0.0, 0.0, 0.0, 0.0}, flips[2] = {0.0, 0.0};          // counts below 2^31: exact in fp64
+        for (int64_t i = threadIdx.x; i < n; i += FID_BLOCK) {
+            const int32_t* c = log_cls + (i * T + task) * V;
+            const double* p = log_p + (i * T + task) * V;
+            const double pk = p[1 + s], pd = p[1 + S + s];
+            a[0] += pk; a[1] += pd; a[2] += p[0] - pd; a[3] += p[0] - pk;
+            flips[0] += c[1 + S + s] != c[0] ? 1.0 : 0.0;
+            flips[1] += c[1 + s] != c[0] ? 1.0 : 0.0;
+        }
+        double t[6];
+        for (int k = 0; k < 4; ++k) t[k] = fid_block_sum(a[k], sh);
+        for (int k = 0; k < 2; ++k) t[4 + k] = fid_block_sum(flips[k], sh);
+        if (threadIdx.x == 0) {
+            out[A + (int64_t)task * S + s] = (int64_t)t[4];
+            out[A + ((int64_t)T + task) * S + s] = (int64_t)t[5];
+            for (int k = 0; k < 4; ++k) out[D + T + ((int64_t)k * T + task) * S + s] = __double_as_longlong(t[k]);
+        }
+    }
+}
+
 }  // namespace gsat
 
 using namespace gsat;
@@ -286,6 +357,40 @@ int gsat_fidelity_curve_reduce(const int32_t* log_cls, const double* log_p, cons
     GSAT_REQUIRE(max_graphs >= 0 && levels >= 1 && levels <= FIDC_MAX_LEVELS && log_state && out && (max_graphs == 0 || (log_cls && log_p)),
                  GSAT_ERR_ARG, "gsat_fidelity_curve_reduce: bad argument");
     k_fidc_reduce<<<1, FID_BLOCK, 0, stream>>>(log_cls, log_p, log_state, max_graphs, (int)levels, out);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_fidelity_curve_append_tasks(const float* logits, int64_t graphs_per_variant, int64_t tasks, int64_t levels, const int32_t* valid,
+                                     const int32_t* stack_valid, int32_t* log_cls, double* log_p, int64_t* log_state, int64_t max_graphs,
+                                     void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(graphs_per_variant >= 0 && tasks >= 1 && max_graphs >= 0 && levels >= 1 && levels <= FIDC_MAX_LEVELS, GSAT_ERR_ARG,
+                 "gsat_fidelity_curve_append_tasks: bad extent (1..16 levels)");
+    GSAT_REQUIRE(tasks <= 1024, GSAT_ERR_UNSUPPORTED, "gsat_fidelity_curve_append_tasks: more than 1024 tasks");
+    const int V = 2 * (int)levels + 1;
+    const int64_t per_graph = tasks * V;                                     // at most 1024 * 33
+    GSAT_REQUIRE(graphs_per_variant < (1ll << 31) / per_graph && max_graphs < (1ll << 31) / per_graph, GSAT_ERR_UNSUPPORTED,
+                 "gsat_fidelity_curve_append_tasks: >2^31 entries");
+    GSAT_REQUIRE(log_state && stack_valid && (graphs_per_variant == 0 || logits) && (max_graphs == 0 || (log_cls && log_p)), GSAT_ERR_ARG,
+                 "gsat_fidelity_curve_append_tasks: null pointer");
+    const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(graphs_per_variant * tasks, FID_BLOCK), 1), FID_MAX_BLOCKS);
+    k_fidt_rows<<<blocks, FID_BLOCK, 0, stream>>>(logits, graphs_per_variant, (int)tasks, V, valid, stack_valid, log_cls, log_p, log_state,
+                                                  max_graphs);
+    GSAT_LAUNCH_CHECK();
+    k_fidc_commit<<<1, 64, 0, stream>>>(graphs_per_variant, V, valid, stack_valid, log_state, max_graphs);
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
+}
+
+int gsat_fidelity_curve_reduce_tasks(const int32_t* log_cls, const double* log_p, const int64_t* log_state, int64_t max_graphs, int64_t levels,
+                                     int64_t tasks, int64_t* out, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GSAT_REQUIRE(max_graphs >= 0 && levels >= 1 && levels <= FIDC_MAX_LEVELS && tasks >= 1 && log_state && out &&
+                 (max_graphs == 0 || (log_cls && log_p)), GSAT_ERR_ARG, "gsat_fidelity_curve_reduce_tasks: bad argument");
+    GSAT_REQUIRE(tasks <= 1024 && max_graphs < (1ll << 31) / (tasks * (2 * levels + 1)), GSAT_ERR_UNSUPPORTED,
+                 "gsat_fidelity_curve_reduce_tasks: more than 1024 tasks or >2^31 entries");
+    k_fidt_reduce<<<(unsigned)tasks, FID_BLOCK, 0, stream>>>(log_cls, log_p, log_state, max_graphs, (int)levels, (int)tasks, out);
     GSAT_LAUNCH_CHECK();
     return GSAT_OK;
 }

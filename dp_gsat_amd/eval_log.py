@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ._lib import GsatHipError, call, ptr, stream
-from .evaluate import MAX_BINS, attention_histogram, classifier_accuracy, classifier_rocauc, pr_curve
+from .evaluate import MAX_BINS, attention_histogram, classifier_accuracy, classifier_rocauc, classifier_rocauc_tasks, pr_curve
 from .explain import _att, _labels, attention_auroc, check_levels, check_rankings, delta_kl_stats, rank_edges_lds_cap
 from .graph_index import call_size, get_index
 
@@ -148,8 +148,10 @@ class EpochLog:
         """Score everything logged since ``reset``: the keys of ``EvaluationMeter.compute()`` with the same meaning -- one global
         attention ROC-AUC, the mean over all graphs of hits / k, the mean over the batches of the per-batch delta-KL, class means,
         histograms and PR curve over all edges, accuracy and ROC-AUC over all graphs -- plus ``loss``, ``pred``, ``info``, the means
-        over the batches (NaN when a batch was appended without ``losses``).  Exactly two host reads: the counts, then the packed
-        results.  ValueError when an append was refused, or nothing was appended."""
+        over the batches (NaN when a batch was appended without ``losses``).  With ``multi_label`` also ``clf_roc_tasks``: numpy
+        float64[T], the per-task ROC-AUCs whose mean over the scorable tasks ``clf_roc`` is (one ``task_auroc_counts`` call gives both), NaN
+        for a task without both classes among its labelled rows.  Exactly two host reads: the counts, then the packed results.
+        ValueError when an append was refused, or nothing was appended."""
         E, Gn, nb, flags, max_graph_edges, max_batch_edges = self._counts()
         if flags & FLAG_OVERFLOW:
             raise ValueError("EpochLog: flag bit 0 is set -- a padded batch did not fit its capacity (valid[3]) and was not logged")
@@ -181,10 +183,15 @@ class EpochLog:
         hist = attention_histogram(a, lab, bins=self.bins)
         acc = classifier_accuracy(logits, y, self.multi_label).view(1) if Gn else f64(float("nan"))
         binary = self.multi_label or self.logit_cols == 1
-        roc = classifier_rocauc(logits, y).view(1) if binary else f64(0.0)
+        roc_tasks = []
+        if self.multi_label:            # the per-task scores ride in the same read, behind everything else
+            roc, per_task = classifier_rocauc_tasks(logits, y)
+            roc, roc_tasks = roc.view(1), [per_task]
+        else:
+            roc = classifier_rocauc(logits, y).view(1) if binary else f64(0.0)
         pr = pr_curve(hist)
         names = ("tp", "fp", "tn", "fn")
-        floats = [attention_auroc(a, lab).view(1), prec, dkl, means, acc, roc, self.loss_sums / float(nb), pr["precision"], pr["recall"]]
+        floats = [attention_auroc(a, lab).view(1), prec, dkl, means, acc, roc, self.loss_sums / float(nb), pr["precision"], pr["recall"]] + roc_tasks
         packed = torch.cat([hist.counts.view(-1), hist.outside] + [pr[n] for n in names] +
                            [t.view(torch.int64) for t in floats]).cpu().numpy()                   # the second host read
         B = self.bins
@@ -196,6 +203,8 @@ class EpochLog:
         curve = {n: ints[2 * B + 2 + i * B:2 * B + 2 + (i + 1) * B].copy() for i, n in enumerate(names)}
         curve.update(precision=fl[10:10 + B].copy(), recall=fl[10 + B:10 + 2 * B].copy())
         res["pr_curve"] = curve
+        if self.multi_label:
+            res["clf_roc_tasks"] = fl[10 + 2 * B:].copy()
         return res
 
 
@@ -280,9 +289,14 @@ class FidelityCurveLog:
 
     ``rankings=R`` (``R * S`` at most 16): the log of a multi-ranking stack (``explanation_stack_multi``, ``V = 1 + 2 R S`` blocks).  The
     same kernels run with ``R * S`` flat levels -- flat level ``r * S + s`` is ranking ``r``, level ``s`` -- and ``compute`` returns the
-    per-level entries as ``[R][S]`` nested lists under the same keys.  With ``rankings=1`` everything is as without it."""
+    per-level entries as ``[R][S]`` nested lists under the same keys.  With ``rankings=1`` everything is as without it.
 
-    def __init__(self, max_graphs: int, classes: int, ks=None, ratios=None, device=None, rankings: int = 1):
+    ``tasks=T`` (``classes == T``, 1 to 1024; not with ``rankings > 1``): the log of a multi-label head, whose every (graph, task) is a
+    binary decision of its own -- class ``z >= 0``, probability ``sigmoid(+-z)``.  ``cls`` and ``p`` become ``[max_graphs, T, V]`` (``state[0]``
+    still counts graphs), ``append`` / ``compute`` go through ``gsat_fidelity_curve_append_tasks`` / ``_reduce_tasks``, and ``compute`` adds
+    the per-task curves (see there).  Without ``tasks`` everything is as before."""
+
+    def __init__(self, max_graphs: int, classes: int, ks=None, ratios=None, device=None, rankings: int = 1, tasks: Optional[int] = None):
         ks, ratios = check_levels(ks, ratios)
         self.levels, self.by_ratio = tuple(ks if ks is not None else ratios), ratios is not None
         self.rankings = check_rankings(rankings, len(self.levels))
@@ -290,16 +304,27 @@ class FidelityCurveLog:
         self.variants = 2 * S + 1
         if int(max_graphs) < 0 or int(classes) < 1:
             raise ValueError("FidelityCurveLog needs a non-negative capacity and at least one logit column")
-        if int(max_graphs) * self.variants >= 2 ** 31:
-            raise ValueError("FidelityCurveLog: max_graphs * variants must be below 2**31")
+        self.tasks = None
+        if tasks is not None:
+            if isinstance(tasks, bool) or int(tasks) != tasks or not 1 <= int(tasks) <= 1024:
+                raise ValueError("FidelityCurveLog: tasks must be an int between 1 and 1024")
+            if self.rankings > 1:
+                raise ValueError("FidelityCurveLog: a task axis together with rankings > 1 is not covered")
+            if int(classes) != int(tasks):
+                raise ValueError("FidelityCurveLog: a multi-label head has one logit column per task (classes == tasks)")
+            self.tasks = int(tasks)
+        if int(max_graphs) * self.variants * (self.tasks or 1) >= 2 ** 31:
+            raise ValueError("FidelityCurveLog: max_graphs * variants (* tasks) must be below 2**31")
         self.max_graphs, self.classes = int(max_graphs), int(classes)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if dev.type != "cuda":
             raise GsatHipError("dp_gsat_amd.eval_log needs a ROCm (cuda) device: the HIP path has no CPU fallback")
-        self.cls = torch.empty((self.max_graphs, self.variants), dtype=torch.int32, device=dev)
-        self.p = torch.empty((self.max_graphs, self.variants), dtype=torch.float64, device=dev)
+        shape = (self.max_graphs, self.variants) if self.tasks is None else (self.max_graphs, self.tasks, self.variants)
+        self.cls = torch.empty(shape, dtype=torch.int32, device=dev)
+        self.p = torch.empty(shape, dtype=torch.float64, device=dev)
         self.state = torch.zeros(20, dtype=torch.int64, device=dev)
-        self._out = torch.empty(5 + 7 * S, dtype=torch.int64, device=dev)
+        out_words = 5 + 7 * S if self.tasks is None else 4 + S + self.tasks * (1 + 6 * S)
+        self._out = torch.empty(out_words, dtype=torch.int64, device=dev)
 
     def reset(self) -> None:
         """Empty the log: one kernel zeroes ``state`` (no memset node, so a captured graph may hold it), nothing is read."""
@@ -318,7 +343,8 @@ class FidelityCurveLog:
         for t, n in zip(words, (4 * self.variants, 4)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() < n or not t.is_cuda:
                 raise ValueError("valid words must be int32 ROCm tensors: (N_real, E_real, B, overflow), one row per variant for the stack")
-        call("gsat_fidelity_curve_append", ptr(z) if z.numel() else None, int(z.shape[0]) // self.variants, self.classes, self._flat,
+        entry = "gsat_fidelity_curve_append" if self.tasks is None else "gsat_fidelity_curve_append_tasks"
+        call(entry, ptr(z) if z.numel() else None, int(z.shape[0]) // self.variants, self.classes, self._flat,
              ptr(valid.contiguous()) if valid is not None else None, ptr(stack_valid.contiguous()), ptr(self.cls) if self.cls.numel() else None,
              ptr(self.p) if self.p.numel() else None, ptr(self.state), self.max_graphs, stream())
 
@@ -327,20 +353,20 @@ class FidelityCurveLog:
         per level, as lists: ``fidelity_plus = mean(p_full - p_drop)``, ``fidelity_minus = mean(p_full - p_keep)``, ``p_keep``, ``p_drop``,
         the exact flip rates ``flip_plus = #(cls_drop != cls_full) / n`` and ``flip_minus = #(cls_keep != cls_full) / n`` and
         ``kept_fraction`` = kept edges / real edges (integer sums); ``p_full`` and ``n``.  fp64 sums in a fixed order: two runs over the same
-        log are bitwise equal.  ValueError when an append was refused, or nothing was appended."""
+        log are bitwise equal.  ValueError when an append was refused, or nothing was appended.
+
+        With ``tasks=T`` every graph counts for every task.  ``fidelity_plus_tasks``, ``fidelity_minus_tasks``, ``p_keep_tasks``,
+        ``p_drop_tasks``, ``flip_plus_tasks`` and ``flip_minus_tasks`` are ``[S][T]`` nested lists and ``p_full_tasks`` is ``[T]``: the means
+        over the ``n`` logged graphs of one task, each from its own fixed-order fp64 sum on the device.  The keys above are then DEFINED as
+        the fp64 mean over the tasks of these per-task means (``numpy.mean``, on the host after the read): the flat mean over all (graph,
+        task) pairs up to rounding."""
         S = self._flat
+        if self.tasks is not None:
+            return self._compute_tasks(S, self.tasks)
         call("gsat_fidelity_curve_reduce", ptr(self.cls) if self.cls.numel() else None, ptr(self.p) if self.p.numel() else None,
              ptr(self.state), self.max_graphs, S, ptr(self._out), stream())
         packed = self._out.cpu().numpy()                                                        # the one host read
-        n, batches, flags, real_edges = (int(v) for v in packed[:4])
-        if flags & FLAG_OVERFLOW:
-            raise ValueError("FidelityCurveLog: flag bit 0 is set -- a padded batch or a variant of its stack did not fit its capacity "
-                             "(valid[3]) and was not logged")
-        if flags & FLAG_FULL:
-            raise ValueError(f"FidelityCurveLog: flag bit 1 is set -- an append would have exceeded max_graphs ({self.max_graphs}) and "
-                             "was not logged")
-        if batches == 0 or n == 0:
-            raise ValueError("FidelityCurveLog.compute() before any append()")
+        n, real_edges = self._counters(packed)
         ints = packed[4:4 + 3 * S].reshape(3, S)
         sums = packed[4 + 3 * S:].view(np.float64)
         per_level = sums[1:].reshape(4, S)
@@ -353,4 +379,38 @@ class FidelityCurveLog:
             per = len(self.levels)
             for key in ("fidelity_plus", "fidelity_minus", "p_keep", "p_drop", "flip_plus", "flip_minus", "kept_fraction"):
                 res[key] = [res[key][r * per:(r + 1) * per] for r in range(self.rankings)]
+        return res
+
+    def _counters(self, packed):
+        """(n, real edges) of a packed result; raises what ``compute`` raises."""
+        n, batches, flags, real_edges = (int(v) for v in packed[:4])
+        if flags & FLAG_OVERFLOW:
+            raise ValueError("FidelityCurveLog: flag bit 0 is set -- a padded batch or a variant of its stack did not fit its capacity "
+                             "(valid[3]) and was not logged")
+        if flags & FLAG_FULL:
+            raise ValueError(f"FidelityCurveLog: flag bit 1 is set -- an append would have exceeded max_graphs ({self.max_graphs}) and "
+                             "was not logged")
+        if batches == 0 or n == 0:
+            raise ValueError("FidelityCurveLog.compute() before any append()")
+        return n, real_edges
+
+    def _compute_tasks(self, S, T):
+        """``compute`` of a log with a task axis: one launch of T workgroups, one host read (layout: include/gsat_hip.h)."""
+        call("gsat_fidelity_curve_reduce_tasks", ptr(self.cls) if self.cls.numel() else None, ptr(self.p) if self.p.numel() else None,
+             ptr(self.state), self.max_graphs, S, T, ptr(self._out), stream())
+        packed = self._out.cpu().numpy()                                                        # the one host read
+        n, real_edges = self._counters(packed)
+        A = 4 + S
+        D = A + 2 * T * S
+        flips = packed[A:D].reshape(2, T, S).astype(np.float64) / n                             # counts below 2^31: exact
+        sums = packed[D:].view(np.float64)
+        full = sums[:T] / n
+        per = sums[T:].reshape(4, T, S) / n                                                     # p_keep, p_drop, p_full - p_drop, p_full - p_keep
+        tasks = {"fidelity_plus": per[2], "fidelity_minus": per[3], "p_keep": per[0], "p_drop": per[1], "flip_plus": flips[0],
+                 "flip_minus": flips[1]}
+        res = {"levels": list(self.levels), "p_full": float(np.mean(full)), "p_full_tasks": [float(v) for v in full],
+               "kept_fraction": [int(v) / real_edges if real_edges else 0.0 for v in packed[4:A]], "n": n}
+        for key, a in tasks.items():                                                            # a: [T, S]
+            res[key + "_tasks"] = [[float(a[t, s]) for t in range(T)] for s in range(S)]
+            res[key] = [float(np.mean(np.array(row, dtype=np.float64))) for row in res[key + "_tasks"]]
         return res

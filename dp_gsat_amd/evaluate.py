@@ -65,11 +65,18 @@ def classifier_rocauc(logits, labels) -> torch.Tensor:
     """The ogb ``Evaluator``'s rocauc as a 0-dim float64 device tensor: the mean of the exact, tie-aware per-task ROC-AUC over the
     tasks that have at least one positive and one negative labelled row; NaN labels are skipped.  When NO task can be scored ogb
     raises a RuntimeError; this function returns NaN instead, because finding out on the host would be a sync."""
+    return classifier_rocauc_tasks(logits, labels)[0]
+
+
+def classifier_rocauc_tasks(logits, labels):
+    """``(classifier_rocauc(logits, labels), per_task)`` from ONE ``task_auroc_counts`` call: ``per_task`` float64[T] on the device, the
+    ROC-AUC of every task, NaN for a task without both classes among its labelled rows."""
     c = task_auroc_counts(logits, labels)
     den = 2 * c[:, 1] * c[:, 2]
     ok = den > 0
     per_task = torch.where(ok, c[:, 0].double() / den.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=c.device))
-    return per_task.sum() / ok.sum().double()                          # 0 / 0 = NaN: no scorable task
+    mean = per_task.sum() / ok.sum().double()                          # 0 / 0 = NaN: no scorable task
+    return mean, torch.where(ok, per_task, torch.full((), float("nan"), dtype=torch.float64, device=c.device))
 
 
 def classifier_accuracy(logits, labels, multi_label: bool = False) -> torch.Tensor:

@@ -93,17 +93,25 @@ class MLP(BatchSequential):
 
 
 class Criterion(nn.Module):
-    """src/utils/get_model.py:19-34."""
+    """src/utils/get_model.py:19-34.
 
-    def __init__(self, num_class, multi_label):
+    ``capturable=True`` (readable as ``capturable``): ``forward`` always goes through ``criterion_valid`` -- the HIP pair, in all three
+    modes -- and never boolean-indexes, so the multi-label criterion can sit inside a captured hipGraph and on padded and ragged
+    batches (``GSAT.forward_pass``, the replay classes); it works on unpadded batches as well (``g_valid=None``: every row).  The one
+    known deviation is ``criterion_valid``'s: a selection with no labelled entry (no row) gives the loss 0 and zero gradients where
+    the torch arithmetic gives NaN.  The default, ``capturable=False``, is the reference's torch arithmetic as before."""
+
+    def __init__(self, num_class, multi_label, capturable=False):
         super().__init__()
         self.num_class = num_class
         self.multi_label = multi_label
+        self.capturable = bool(capturable)
 
     def forward(self, logits, targets, g_valid=None):
         """``g_valid`` (one int32 on the device): the criterion of the first ``g_valid`` rows alone, through libgsat_hip
-        (``criterion_valid``) -- the graph count of a ragged batch; None: the reference's torch arithmetic."""
-        if g_valid is not None:
+        (``criterion_valid``) -- the graph count of a ragged batch; None: the reference's torch arithmetic, or, ``capturable``, every
+        row through ``criterion_valid``."""
+        if g_valid is not None or self.capturable:
             return criterion_valid(logits, targets, self.num_class, self.multi_label, g_valid)
         if self.num_class == 2 and not self.multi_label:
             return F.binary_cross_entropy_with_logits(logits, targets.float())

@@ -185,11 +185,14 @@ class GSAT(nn.Module):
         loss count its real rows, the criterion sees the real graphs ``[:B]``, and ``data.r`` -- one float on the device, when present -- is
         the info loss's r instead of get_r(epoch).  Every returned tensor has capacity shape; callers slice with the counts.  On a
         ``ragged`` batch (``collate_padded(..., ragged=True)``) the criterion takes the ``B`` graph slots and reads how many are filled from
-        ``valid[2]`` on the device (``criterion_valid``)."""
+        ``valid[2]`` on the device (``criterion_valid``).  A criterion constructed with ``capturable=True`` -- the only way to the
+        multi-label criterion here -- reads the count of real graphs from ``valid[2]`` on every padded batch, fixed-count or ragged, and
+        never loads a row at or beyond it; an overflow batch counts no graph, so its prediction loss is exactly 0 with zero gradient."""
         valid = getattr(data, "valid", None)
         if valid is not None:
-            if getattr(self.criterion, "multi_label", False):
-                raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)")
+            if getattr(self.criterion, "multi_label", False) and not getattr(self.criterion, "capturable", False):
+                raise ValueError("a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable); "
+                                 "construct it as Criterion(num_class, True, capturable=True)")
             with padded(valid, (int(data.x.shape[0]), int(data.edge_index.shape[1]))):
                 return self._forward_pass(data, epoch, training, noise, dropout_masks, loss_weights, int(data.num_graphs) - 1)
         return self._forward_pass(data, epoch, training, noise, dropout_masks, loss_weights, None)
@@ -212,6 +215,9 @@ class GSAT(nn.Module):
             loss, loss_dict = self.__loss__(att, clf_logits, data.y, epoch, loss_weights)
         else:           # static slices: the padding graph is the last one and B is a host int
             g_valid = data.valid[2:3] if getattr(data, "ragged", False) else None        # filled slots, read by the criterion kernel
+            if g_valid is None and getattr(self.criterion, "capturable", False):
+                # a fixed-count batch keeps B in valid[2] when it overflows: its overflow word empties the count (a ragged one's is 0)
+                g_valid = data.valid[2:3] * (1 - data.valid[3:4])
             loss, loss_dict = self.__loss__(att, clf_logits[:real_graphs], data.y[:real_graphs], epoch, loss_weights,
                                             r_dev=getattr(data, "r", None), g_valid=g_valid)
         return edge_att, loss, loss_dict, clf_logits

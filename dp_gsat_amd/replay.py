@@ -27,6 +27,19 @@ from .padding import padded
 from .subgraph import edge_subgraph_padded, explanation_stack, explanation_stack_multi
 
 _MULTI_LABEL = "a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)"
+_MULTI_LABEL_HINT = _MULTI_LABEL + "; construct it as Criterion(num_class, True, capturable=True)"
+_MULTI_LABEL_SINGLE = ("ReplayedFidelity does not cover the multi-label criterion; a single level of a multi-task model is "
+                       "ReplayedFidelityCurve(ks=(k,)) or ReplayedFidelityCurve(ratios=(r,)) with a capturable criterion")
+
+
+def _multi_label(criterion):
+    return bool(getattr(criterion, "multi_label", False))
+
+
+def _refuse_uncapturable(criterion):
+    """The multi-label criterion is taken only when constructed as capturable."""
+    if _multi_label(criterion) and not getattr(criterion, "capturable", False):
+        raise ValueError(_MULTI_LABEL_HINT)
 
 
 # ---- what capturing changes, and what puts it back -------------------------------------------------------------------------------------------
@@ -356,15 +369,21 @@ class ReplayedStep(_Replayed, _TrainingLog):
     ``torch.tensor([...], device=...)`` of the floats).  Warm-up and capture leave the log empty.  Logging reads the step's outputs and
     writes only the log: it draws nothing from the device seed stream or torch's generators and touches no parameter, buffer or
     optimizer state, so a run with ``log_k`` trains bit for bit like one without.  A step that did not fit the capacity appends nothing
-    and makes ``epoch_scores()`` raise.  Without ``log_k`` the captured graph is the one described above, launch for launch."""
+    and makes ``epoch_scores()`` raise.  Without ``log_k`` the captured graph is the one described above, launch for launch.
+
+    Multi-task datasets: a model whose criterion is ``Criterion(T, True, capturable=True)`` is taken, ``ragged`` or not (without
+    ``capturable=True`` the multi-label criterion stays refused, with a ValueError that names the keyword).  The criterion kernels count
+    the labelled entries of the real graphs on the device; an overflow batch counts none, so its prediction loss is exactly 0.  With
+    ``log_k`` the log is made with the criterion's ``multi_label`` and ``epoch_scores()`` adds ``clf_roc_tasks``.  An OGB-style dataset
+    has no edge labels, and ``log_k`` needs some: pack it with ``edge_label_all = zeros(E)`` -- the reference zero-fills ``edge_label``
+    (src/utils/utils.py:31-32) -- and ``att_auroc`` and ``precision@k`` are then 0 by the one-class rule, as the reference reports them."""
 
     def __init__(self, gsat, dataset, batch_size: int, capacity: Optional[tuple] = None, keep_edge_att: bool = False, graph=None,
                  ragged: bool = False, log_k: Optional[int] = None, bins: int = 64, max_graphs: Optional[int] = None,
                  max_edges: Optional[int] = None):
         _check_log_sizes(log_k, bins)
         _need_capturable(gsat.optimizer, "ReplayedStep needs a capturable optimizer")
-        if getattr(gsat.criterion, "multi_label", False):
-            raise ValueError(_MULTI_LABEL)
+        _refuse_uncapturable(gsat.criterion)
         self.gsat, self.dataset = gsat, dataset
         self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
         _training_log_setup(self, log_k, bins, max_graphs, max_edges)
@@ -505,7 +524,8 @@ def _new_logs(ev, count, logits, k, bins, max_graphs, max_edges):
     me = int(ds.edge_local_all.shape[1]) if max_edges is None else int(max_edges)
     # budget batching may close a batch after any graph: at worst one graph per batch
     most = mg if ev.ragged else -(-mg // ev.batch_size)
-    return [EpochLog(k, mg, me, max(most, 1), int(logits.shape[1]), y_cols, bins, False, ds.x_all.device) for _ in range(count)]
+    multi = _multi_label(getattr(ev._model, "criterion", None))           # a DualGSAT has refused its multi-label criteria
+    return [EpochLog(k, mg, me, max(most, 1), int(logits.shape[1]), y_cols, bins, multi, ds.x_all.device) for _ in range(count)]
 
 
 def _check_log_sizes(k, bins):
@@ -584,8 +604,14 @@ class ReplayedEval(_Replayed):
 
     After a step: ``edge_att`` [E_cap, 1], ``clf_logits`` [B + 1, C], ``losses`` [3] and ``batch`` hold the replay's outputs until the next.
 
-    Refused with ValueError, like the padded path: the multi-label criterion, ``sync_group`` BatchNorm, and ``DualGSAT`` (see
-    ``ReplayedDualEval``).
+    Refused with ValueError, like the padded path: a multi-label criterion that was not constructed with ``capturable=True``,
+    ``sync_group`` BatchNorm, and ``DualGSAT`` (see ``ReplayedDualEval``).
+
+    Multi-task datasets: with ``Criterion(T, True, capturable=True)`` the log is an ``EpochLog(..., multi_label=True)`` whose ``y_cols``
+    is the dataset's label width, and ``run`` adds ``clf_roc_tasks`` (numpy float64[T], NaN for a task without both classes among its
+    labelled rows) to ``clf_roc``, the ogb mean over the scorable tasks.  A dataset without edge labels -- the OGB sets -- is packed with
+    ``edge_label_all = zeros(E)``, as the reference zero-fills ``edge_label`` (src/utils/utils.py:31-32): ``att_auroc`` and
+    ``precision@k`` are then 0 by the one-class rule, as the reference reports them (run_gsat.py:761-763).
 
     ``ragged=True``: as in ``ReplayedStep`` -- ``batch_size`` graph slots, ``step`` takes 1 to ``batch_size`` ids, and ``run`` packs its ids
     with ``budget_batches`` and replays EVERY batch: there is no eager tail.  The log then has room for one batch per graph."""
@@ -594,8 +620,7 @@ class ReplayedEval(_Replayed):
                  max_graphs: Optional[int] = None, max_edges: Optional[int] = None, graph=None, ragged: bool = False):
         if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
             raise ValueError("ReplayedEval replays GSAT.forward_pass; the dual/primal evaluation (DualGSAT) is ReplayedDualEval's")
-        if getattr(gsat.criterion, "multi_label", False):
-            raise ValueError(_MULTI_LABEL)
+        _refuse_uncapturable(gsat.criterion)
         _refuse_sync_group(gsat)
         if dataset.edge_label_all is None or dataset.y_all is None:
             raise ValueError("ReplayedEval needs a dataset with edge labels and graph labels")
@@ -788,8 +813,11 @@ class ReplayedFidelity(_Replayed):
     fidelity epoch between ``ReplayedStep`` steps leaves the training run bitwise unchanged.
 
     Refused with ValueError before anything is captured: both or neither of ``k`` and ``ratio``; a dataset without graph labels (edge
-    labels are NOT needed); ``DualGSAT``; ``sync_group`` BatchNorm; the multi-label criterion; a dataset whose largest graph has more
-    edges than ``rank_edges_lds_cap()`` (the radix ranking is not captured); a capacity the first batch does not fit."""
+    labels are NOT needed); ``DualGSAT``; ``sync_group`` BatchNorm; the multi-label criterion, capturable or not; a dataset whose largest
+    graph has more edges than ``rank_edges_lds_cap()`` (the radix ranking is not captured); a capacity the first batch does not fit.
+
+    This single-level class keeps no task axis.  A single level of a multi-task model is ``ReplayedFidelityCurve(..., ks=(k,))`` or
+    ``ReplayedFidelityCurve(..., ratios=(r,))``, whose log has one."""
 
     def __init__(self, gsat, dataset, batch_size: int, k: Optional[int] = None, ratio: Optional[float] = None,
                  capacity: Optional[tuple] = None, max_graphs: Optional[int] = None, graph=None, ragged: bool = False):
@@ -801,8 +829,8 @@ class ReplayedFidelity(_Replayed):
             raise ValueError("ratio must lie in (0, 1]")
         if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
             raise ValueError("ReplayedFidelity replays GSAT.forward_pass and its backbone; DualGSAT fidelity is not covered")
-        if getattr(gsat.criterion, "multi_label", False):
-            raise ValueError(_MULTI_LABEL)
+        if _multi_label(gsat.criterion):
+            raise ValueError(_MULTI_LABEL_SINGLE)
         _refuse_sync_group(gsat)
         if dataset.y_all is None:
             raise ValueError("ReplayedFidelity needs a dataset with graph labels (the eval-mode forward takes them); edge labels are not needed")
@@ -904,17 +932,20 @@ class ReplayedFidelityCurve(_Replayed):
     epoch between ``ReplayedStep`` steps leaves the training run bitwise unchanged.
 
     Refused with ValueError before anything is captured: what ``ReplayedFidelity`` refuses -- a dataset without graph labels, ``DualGSAT``,
-    ``sync_group`` BatchNorm, the multi-label criterion, a dataset whose largest graph has more edges than ``rank_edges_lds_cap()``, a
-    capacity the first batch does not fit -- and bad levels: neither or both of ``ks`` and ``ratios``, values that are not strictly
-    increasing, more than 16."""
+    ``sync_group`` BatchNorm, a dataset whose largest graph has more edges than ``rank_edges_lds_cap()``, a capacity the first batch does
+    not fit --, a multi-label criterion that was not constructed with ``capturable=True``, and bad levels: neither or both of ``ks`` and
+    ``ratios``, values that are not strictly increasing, more than 16.
+
+    Multi-task models (``Criterion(T, True, capturable=True)``): the log is a ``FidelityCurveLog(..., tasks=T)`` -- every (graph, task) is
+    a binary decision of its own -- and ``run`` adds ``fidelity_plus_tasks``, ``fidelity_minus_tasks``, ``p_keep_tasks``, ``p_drop_tasks``,
+    ``flip_plus_tasks``, ``flip_minus_tasks`` (``[S][T]``) and ``p_full_tasks`` (``[T]``); the per-level keys are the means over the tasks."""
 
     def __init__(self, gsat, dataset, batch_size: int, ks=None, ratios=None, capacity: Optional[tuple] = None,
                  max_graphs: Optional[int] = None, graph=None, ragged: bool = False):
         self.ks, self.ratios = _explain.check_levels(ks, ratios)
         if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
             raise ValueError("ReplayedFidelityCurve replays GSAT.forward_pass and its backbone; DualGSAT fidelity is not covered")
-        if getattr(gsat.criterion, "multi_label", False):
-            raise ValueError(_MULTI_LABEL)
+        _refuse_uncapturable(gsat.criterion)
         _refuse_sync_group(gsat)
         if dataset.y_all is None:
             raise ValueError("ReplayedFidelityCurve needs a dataset with graph labels (the eval-mode forward takes them); edge labels are "
@@ -938,7 +969,8 @@ class ReplayedFidelityCurve(_Replayed):
         with torch.no_grad(), padded(b.valid, b.capacity):
             get_index(b.edge_index, int(b.x.shape[0])).graphs(b.batch, int(b.num_graphs))
             logits = self.gsat.clf(b.x, b.edge_index, b.batch, getattr(b, "edge_attr", None))
-        self.log = FidelityCurveLog(self._max_graphs, int(logits.shape[1]), self.ks, self.ratios, self.dataset.x_all.device)
+        tasks = int(logits.shape[1]) if _multi_label(self.gsat.criterion) else None
+        self.log = FidelityCurveLog(self._max_graphs, int(logits.shape[1]), self.ks, self.ratios, self.dataset.x_all.device, tasks=tasks)
 
     def _forward(self, b, epoch=0):
         """Attention, levels, the stack, the one backbone forward and the append for batch ``b`` -- a ``PaddedBatch`` (the captured body)

@@ -1073,6 +1073,35 @@ int gsat_fidelity_curve_reduce(const int32_t* log_cls, const double* log_p, cons
 int gsat_fidelity_curve_reset(int64_t* log_state, void* stream);
 
 /*
+ * gsat_fidelity_curve_append for a multi-label head: logits fp32[V * graphs_per_variant, tasks], and every (graph, task) is a binary
+ * decision of its own -- class z >= 0, probability sigmoid(+-z), the one-logit rules of gsat_fidelity_append.  valid, stack_valid, the
+ * graph count g, log_state int64[20] (log_state[0] counts GRAPHS), the two-launch shape, the commit and the flag rules are those of
+ * gsat_fidelity_curve_append.  Per graph i < g at slot g0 + i and task t, with c = the class of logits[i][t] in block 0:
+ *   log_cls int32[max_graphs, tasks, V]   the class of entry t predicted from every block
+ *   log_p  double[max_graphs, tasks, V]   the probability of c under every block
+ * One thread per (graph, task), the task running fastest; rows at or beyond g are never loaded.  With tasks = 1 the log is, bit for bit,
+ * that of gsat_fidelity_curve_append with classes = 1.  1 <= tasks <= 1024 (the criterion's limit) and levels <= 16;
+ * graphs_per_variant * tasks * V or max_graphs * tasks * V at or above 2^31: GSAT_ERR_UNSUPPORTED.
+ */
+int gsat_fidelity_curve_append_tasks(const float* logits, int64_t graphs_per_variant, int64_t tasks, int64_t levels, const int32_t* valid,
+                                     const int32_t* stack_valid, int32_t* log_cls, double* log_p, int64_t* log_state, int64_t max_graphs,
+                                     void* stream);
+
+/*
+ * One launch of `tasks` workgroups of 256 threads, workgroup t for task t: thread k adds graphs k, k + 256, ... in that order in fp64,
+ * then a fixed-order sum over the workgroup.  No atomics: bitwise repeatable, and with tasks = 1 the sums of gsat_fidelity_curve_reduce
+ * bit for bit.  With S = levels, T = tasks, A = 4 + S and D = A + 2 T S, out int64[4 + S + T (1 + 6 S)] is
+ *   out[0 .. 3]                    graphs, batches, flags, real edges
+ *   out[4 + s]                     kept edges of level s
+ *   out[A + (0 T + t) S + s]       #(cls_drop_s != cls_full) of task t
+ *   out[A + (1 T + t) S + s]       #(cls_keep_s != cls_full) of task t
+ *   out[D + t]                     the bit pattern of a double: the sum of p_full of task t
+ *   out[D + T + (k T + t) S + s]   bit patterns, k = 0 .. 3: the sums of p_keep_s, p_drop_s, p_full - p_drop_s, p_full - p_keep_s of task t
+ */
+int gsat_fidelity_curve_reduce_tasks(const int32_t* log_cls, const double* log_p, const int64_t* log_state, int64_t max_graphs, int64_t levels,
+                                     int64_t tasks, int64_t* out, void* stream);
+
+/*
  * gsat_fidelity_stack for `rankings` explanations of the same edges around ONE full variant: level uint8[rankings, E], row r being what
  * gsat_fidelity_levels writes for ranking r with the same `levels`.  rankings, levels >= 1 and rankings * levels <= 16 (GSAT_ERR_ARG
  * otherwise).  With R = rankings and S = levels there are V = 1 + 2 R S variants:
