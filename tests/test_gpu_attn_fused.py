@@ -39,8 +39,9 @@ def _sized_batch(sizes, seed, undirected=True, isolated=True):
     return ei, torch.tensor(batch, dtype=torch.int64), off
 
 
-def _run(dev, emb, params, ei, batch, G_, edge_mode, training, p, masks, u, fused, seed=7):
-    """One gsat_attn_fwd call through the C ABI; returns every output / saved tensor."""
+def _run(dev, emb, params, ei, batch, G_, edge_mode, training, p, masks, u, fused, seed=7, seed_dev=None):
+    """One gsat_attn_fwd call through the C ABI; returns every output / saved tensor.  Without ``masks`` / ``u`` the kernels draw them
+    from ``seed``, or from the device word ``seed_dev`` when given."""
     from dp_gsat_amd import _lib
     from dp_gsat_amd._lib import call, ptr, stream
     from dp_gsat_amd.graph_index import BatchIndex
@@ -59,14 +60,15 @@ def _run(dev, emb, params, ei, batch, G_, edge_mode, training, p, masks, u, fuse
     logits = torch.full((M, 1), float("nan"), dtype=f32, device=dev)
     att = torch.full((M, 1), float("nan"), dtype=f32, device=dev)
     m1, m2 = masks if masks is not None else (None, None)
-    args = _attn_args(emb, params, index, seg, edge_mode, training, p, seed, m1, m2, u, (P, Q, a1, h2, stats, logits, att), None, u is None and training)
+    args = _attn_args(emb, params, index, seg, edge_mode, training, p, seed, m1, m2, u, (P, Q, a1, h2, stats, logits, att), seed_dev, u is None and training)
     args.fused = 1 if fused else -1
     n = int(_lib.load().gsat_attn_fwd_workspace_bytes(ctypes.byref(args)))
     ws = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
     args.fwd_workspace, args.fwd_workspace_bytes = ptr(ws), n
+    kind = int(_lib.load().gsat_attn_fwd_kind(ctypes.byref(args)))           # 0 staged / 1 fused fp32 / 2 fused split-bf16 x 6
     call("gsat_attn_fwd", ctypes.byref(args), stream())
     torch.cuda.synchronize()
-    return dict(P=P, Q=Q, a1=a1, h2=h2, stats=stats, logits=logits, att=att)
+    return dict(P=P, Q=Q, a1=a1, h2=h2, stats=stats, logits=logits, att=att, kind=kind)
 
 
 def _params(H, edge_mode, dev, seed, C1=None, C2=None):
@@ -203,8 +205,10 @@ def test_fused_extractor_module_vs_oracle_with_big_graph(dev, edge_mode, monkeyp
         close(p.grad, r32[k], ref64=r64[k], what=k)
 
 
-def _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dlogits, datt, fused_bwd, monkeypatch, p=0.5, training=True):
-    """gsat_attn_fwd (staged) + gsat_attn_bwd through the C ABI; returns the gradients."""
+def _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dlogits, datt, fused_bwd, monkeypatch, p=0.5, training=True, seed=7,
+             seed_dev=None, saved=False):
+    """gsat_attn_fwd (staged) + gsat_attn_bwd through the C ABI; returns the gradients and, with ``saved``, also what the forward wrote.
+    Without ``masks`` / ``u`` both passes draw them from ``seed``, or from the device word ``seed_dev`` when given."""
     from dp_gsat_amd import _lib
     from dp_gsat_amd._lib import AttnGrads, call, ptr, stream
     from dp_gsat_amd.graph_index import BatchIndex
@@ -219,7 +223,7 @@ def _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dlogits, datt
     mk = lambda *s: torch.empty(*s, dtype=f32, device=dev)
     bufs = (mk(N, C1), mk(N, C1) if edge_mode else None, mk(M, C1), mk(M, C2), mk(max(G_, 1) * (2 * C1 + 2 * C2)), mk(M, 1), mk(M, 1))
     m1, m2 = masks if masks is not None else (None, None)
-    args = _attn_args(emb, params, index, seg, edge_mode, training, p, 7, m1, m2, u, bufs, None, u is None and training)
+    args = _attn_args(emb, params, index, seg, edge_mode, training, p, seed, m1, m2, u, bufs, seed_dev, u is None and training)
     args.fused = -1
     n = int(_lib.load().gsat_attn_fwd_workspace_bytes(ctypes.byref(args)))
     ws = torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
@@ -240,7 +244,10 @@ def _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dlogits, datt
     g.workspace, g.workspace_bytes = ptr(wsb), nb
     call("gsat_attn_bwd", ctypes.byref(args), ctypes.byref(g), stream())
     torch.cuda.synchronize()
-    return dict(demb=demb, dW1=grads[0], db1=grads[1], dW2=grads[2], db2=grads[3], dW3=grads[4], db3=grads[5])
+    out = dict(demb=demb, dW1=grads[0], db1=grads[1], dW2=grads[2], db2=grads[3], dW3=grads[4], db3=grads[5])
+    if saved:
+        out.update({k: t for k, t in zip(("P", "Q", "a1", "h2", "stats", "logits", "att"), bufs) if t is not None})
+    return out
 
 
 BWD_CASES = {
