@@ -77,6 +77,7 @@ SIGNATURES = {
     "gsat_gemm_pair_x3": (INT, [I64, I64, I64, I64, P, I64, P, I64, P, I64, P, I64, P, I64, INT, P, SZ, P]),
     "gsat_attn_fwd_workspace_bytes": (SZ, [P]),
     "gsat_attn_fwd_kind": (I32, [P]),
+    "gsat_attn_paths": (INT, [P, P, INT]),
     "gsat_attn_bwd_workspace_bytes": (SZ, [P]),
     "gsat_attn_fwd": (INT, [P, P]),
     "gsat_attn_bwd": (INT, [P, P, P]),
@@ -181,6 +182,18 @@ _lib = None
 
 class GsatHipError(RuntimeError):
     pass
+
+
+# slots of gsat_attn_paths, in the order of the GSAT_ATTN_PATH_* indices of include/gsat_hip.h
+ATTN_PATH_FIELDS = ("fwd_kind", "fwd_pqg", "fwd_nrb", "fwd_ncbw", "slices", "bwd_fused", "bwd_ncht", "bwd_dual_l2", "bwd_dual_l1",
+                    "bwd_pair_l2", "bwd_pair_l1", "bwd_split", "bwd_merged")
+
+
+def attn_paths(args):
+    """gsat_attn_paths(args) as a dict: what gsat_attn_fwd / gsat_attn_bwd would run for this AttnArgs under the current environment."""
+    out = (c_int32 * len(ATTN_PATH_FIELDS))()
+    call("gsat_attn_paths", ctypes.byref(args), out, len(ATTN_PATH_FIELDS))
+    return dict(zip(ATTN_PATH_FIELDS, (int(v) for v in out)))
 
 
 def load():

@@ -28,14 +28,18 @@ constexpr int SB_RC = 2;         // rows per slot kept in registers across the p
 // row-major C[M,N] = alpha(=1) * op(A) op(B) + beta(0|1) * C through the hand-written MFMA GEMM (gemm.hip).
 // ta: A is given as [K,M]; tb: B is given as [N,K] (nn.Linear weight layout).
 struct GemmWs { float* ptr; size_t floats; };
+// env GSAT_ATTN_BWD_SPLIT=0: the backward products as exact fp32 MFMA.  Read per call: bench.py times both settings in one process
+static bool bwd_split_on() {
+    const char* env = getenv("GSAT_ATTN_BWD_SPLIT");
+    return !(env && atoi(env) == 0);
+}
 // `split_ok`: the product may run as split-bf16 (relative error ~1e-5 of |A||B|).  Only the BACKWARD products qualify: their
 // results pass through linear maps only (rstd * (dy - mean(dy) - y mean(dy y)), further GEMMs), so the relative error stays
 // 1e-5 of each gradient's own scale.  The forward products feed an InstanceNorm directly: 1/sigma of a nearly constant channel
 // turns the same perturbation of h into ~3e2 x 1e-5 of the normalised value, so they stay exact fp32.
 static int gemm_rm(hipStream_t stream, bool ta, bool tb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
                    int64_t ldb, float beta, float* C, int64_t ldc, GemmWs ws = {nullptr, 0}, bool split_ok = false, SlabJob* defer = nullptr) {
-    const char* env = getenv("GSAT_ATTN_BWD_SPLIT");                    // read per call: bench.py times both settings in one process
-    const bool bwd_split = !(env && atoi(env) == 0);
+    const bool bwd_split = bwd_split_on();
     // the weight gradients dh^T x of the backward (A and B both reduction-major): the streaming kernel where its plan says eligible,
     // else the same gemm_f32 call as below
     if (ta && !tb && split_ok && bwd_split) return gemm_wgrad(stream, M, N, K, A, lda, B, ldb, C, ldc, beta != 0.f, ws.ptr, ws.floats, defer);
@@ -43,8 +47,7 @@ static int gemm_rm(hipStream_t stream, bool ta, bool tb, int64_t M, int64_t N, i
 }
 // whether the backward's OUT[R,Co] = G W and DW[Cg,Cy] = G^T Y go out as one launch (gemm_pair_x3): the split-bf16 leg only
 static bool pair_ok(int64_t R, int64_t Cg, int64_t Co, int64_t Cy) {
-    const char* env = getenv("GSAT_ATTN_BWD_SPLIT");
-    return !(env && atoi(env) == 0) && gemm_pair_plan(R, Cg, Co, Cy).paired;
+    return bwd_split_on() && gemm_pair_plan(R, Cg, Co, Cy).paired;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -748,6 +751,38 @@ static int check_args(const gsat_attn_args* a, const char* who) {
     return GSAT_OK;
 }
 
+// Every choice gsat_attn_bwd makes between kernels, from the arguments and the environment alone.  gsat_attn_bwd branches on these fields
+// and gsat_attn_paths reports them: one evaluation of the predicates, nothing restated.
+struct BwdPaths {
+    bool fused;          // one launch from (dlogits, datt) down to dh1 (attn_fused_bwd.hip); false: the staged kernels
+    int ncht;            // fused: layer-1 chunks of its kernel template
+    bool split;          // products as split-bf16 (false: exact fp32 MFMA, GSAT_ATTN_BWD_SPLIT=0)
+    bool merged;         // staged: dW3 / db3 finished from the head kernel's partials in one launch (false: two two-stage column sums)
+    bool dual2, pair2;   // staged, da1 | dW2: the dual tile kernel (dual_gemm.hip) / one k_pair_x3 launch / neither: two GEMM calls
+    bool dual1, pair1;   // demb | dW1 likewise (edge mode never pairs: its products run on dP and dQ)
+};
+static BwdPaths attn_bwd_paths(const gsat_attn_args* a) {
+    const int64_t M = a->M, N = a->N, G = a->G;
+    const int H = a->H, C1 = a->C1, C2 = a->C2;
+    BwdPaths p{};
+    const int Z = seg_slices(M, G);
+    p.fused = attn_fused_bwd_eligible(a) && Z == 1;
+    p.ncht = p.fused ? attn_fused_bwd_ncht(a) : 0;
+    p.split = bwd_split_on();
+    if (!p.fused) {
+        // env GSAT_ATTN_BWD_MERGED=0: the round-2 sequence (two-stage column sums for db3 and dW3) also for unsliced segments (A/B switch).
+        // The per-block sums of dz live in the column-sum scratch: 256 * max(C1, C2) >= M / 256 floats for M < 2^24 C
+        const char* env_m = getenv("GSAT_ATTN_BWD_MERGED");
+        const bool part_ok = (size_t)ceil_div(M, 256) <= (size_t)256 * std::max(C1, C2);
+        p.merged = Z == 1 && G > 0 && !(env_m && atoi(env_m) == 0) && part_ok;
+        p.dual2 = dual_gemm_ok(1, M, C2, C1, C1);
+        p.pair2 = !p.dual2 && pair_ok(M, C2, C1, C1);
+    }
+    p.dual1 = dual_gemm_ok(2, N, C1, H, H);
+    p.pair1 = !a->edge_mode && !p.dual1 && pair_ok(N, C1, H, H);
+    return p;
+}
+
 }  // namespace gsat
 
 using namespace gsat;
@@ -846,6 +881,31 @@ int gsat_attn_fwd_kind(const gsat_attn_args* a) {
     return fg.x6 ? 2 : 1;
 }
 
+/* what gsat_attn_fwd and gsat_attn_bwd would run for these arguments under the current environment; see include/gsat_hip.h */
+int gsat_attn_paths(const gsat_attn_args* a, int32_t* out, int n) {
+    GSAT_REQUIRE(a && out && n >= GSAT_ATTN_PATHS_N, GSAT_ERR_ARG, "gsat_attn_paths: null argument or fewer than %d slots", GSAT_ATTN_PATHS_N);
+    int32_t v[GSAT_ATTN_PATHS_N] = {};
+    FusedGeom fg;
+    if (attn_fused_eligible(a, &fg)) {
+        v[GSAT_ATTN_PATH_FWD_KIND] = fg.x6 ? 2 : 1;
+        v[GSAT_ATTN_PATH_FWD_PQG] = fg.pqg;
+        v[GSAT_ATTN_PATH_FWD_NRB] = fg.NRB;
+        v[GSAT_ATTN_PATH_FWD_NCBW] = fused_ncbw(fg);
+    }
+    v[GSAT_ATTN_PATH_SLICES] = seg_slices(a->M, a->G);
+    const BwdPaths bp = attn_bwd_paths(a);
+    v[GSAT_ATTN_PATH_BWD_FUSED] = bp.fused;
+    v[GSAT_ATTN_PATH_BWD_NCHT] = bp.ncht;
+    v[GSAT_ATTN_PATH_BWD_DUAL_L2] = bp.dual2;
+    v[GSAT_ATTN_PATH_BWD_DUAL_L1] = bp.dual1;
+    v[GSAT_ATTN_PATH_BWD_PAIR_L2] = bp.pair2;
+    v[GSAT_ATTN_PATH_BWD_PAIR_L1] = bp.pair1;
+    v[GSAT_ATTN_PATH_BWD_SPLIT] = bp.split;
+    v[GSAT_ATTN_PATH_BWD_MERGED] = bp.merged;
+    memcpy(out, v, sizeof(v));
+    return GSAT_OK;
+}
+
 size_t gsat_attn_bwd_workspace_bytes(const gsat_attn_args* a) {
     if (!a) return 0;
     const size_t M = (size_t)a->M, N = (size_t)a->N, G = (size_t)a->G, C1 = a->C1, C2 = a->C2;
@@ -916,7 +976,8 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
     SlabJob jobs[3] = {};                        // pending ordered sums of dW2, dW1 (| its two halves): one launch at the end
     const size_t dws_bytes = std::max(dual_gemm_ws_bytes(1, C2, C1, C1), dual_gemm_ws_bytes(2, C1, H, H));
     char* dws = ar.take<char>(dws_bytes);
-    const bool fused_bwd = attn_fused_bwd_eligible(a) && seg_slices(M, G) == 1;
+    const BwdPaths bp = attn_bwd_paths(a);
+    const bool fused_bwd = bp.fused;
     const size_t fws_bytes = fused_bwd ? attn_fused_bwd_ws_bytes(a) : 0;
     char* fws = fused_bwd ? ar.take<char>(fws_bytes) : nullptr;
     GSAT_REQUIRE(ar.ok(), GSAT_ERR_WORKSPACE, "gsat_attn_bwd: workspace %zu < %zu", gr->workspace_bytes, ar.off);
@@ -932,17 +993,14 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
     if (fused_bwd) {          // one launch from (dlogits, datt) down to dh1 (in the da1 buffer), dW2 / dW3 / db3 included (attn_fused_bwd.hip)
         if ((rc = attn_fused_bwd(stream, a, gr, da1, fws, fws_bytes))) return rc;
     } else {
-    // env GSAT_ATTN_BWD_MERGED=0: the round-2 sequence (two-stage column sums for db3 and dW3) also for unsliced segments (A/B switch)
-    const char* env_m = getenv("GSAT_ATTN_BWD_MERGED");
-    const bool merged = Z == 1 && G > 0 && !(env_m && atoi(env_m) == 0);
+    const bool merged = bp.merged;
     const unsigned dzb = (unsigned)ceil_div(M, 256);
-    float* dzpart = scratch;                         // [dzb] per-block sums of dz; `scratch` holds 256 * max(C1, C2) >= M / 256 floats for M < 2^24 C
-    const bool part_ok = (size_t)dzb <= (size_t)256 * std::max(C1, C2);
+    float* dzpart = scratch;                         // [dzb] per-block sums of dz
     // b1 and b2 sit in front of an InstanceNorm, which removes any per-channel constant of its segment: their
     // gradients are exactly zero (the reference's autograd returns ~1e-7 rounding noise of a cancelling sum).
-    k_dz<<<dzb, 256, 0, stream>>>(gr->dlogits, gr->datt, a->att, M, dz, gr->db1, (int)C1, gr->db2, (int)C2, (merged && part_ok) ? dzpart : nullptr);
+    k_dz<<<dzb, 256, 0, stream>>>(gr->dlogits, gr->datt, a->att, M, dz, gr->db1, (int)C1, gr->db2, (int)C2, merged ? dzpart : nullptr);
     GSAT_LAUNCH_CHECK();
-    if (!(merged && part_ok) && (rc = colsum(stream, dz, M, 1, gr->db3, scratch))) return rc;
+    if (!merged && (rc = colsum(stream, dz, M, 1, gr->db3, scratch))) return rc;
     // ---- through the head and the second InstanceNorm ------------------------------------------
     if (Z == 1)          // statistics and dh2 in one launch
         k_head_bwd_stats<true><<<g2, SB, 0, stream>>>(a->h2, a->b2, a->seg_ptr, a->seg_order, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop,
@@ -950,7 +1008,7 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
     else
         k_head_bwd_stats<false><<<g2, SB, 0, stream>>>(a->h2, a->b2, a->seg_ptr, a->seg_order, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop,
                                                        a->training, a->W3, DzSrc{dz, nullptr, nullptr, nullptr}, C2, zp1, zp2, zp3);
-    if (merged && part_ok)       // dW3 and db3 from the partials, one launch (instead of two two-stage column sums)
+    if (merged)     // dW3 and db3 from the partials, one launch (instead of two two-stage column sums)
         k_head_bwd_finish<<<(unsigned)ceil_div(C2, 4 * SB_LANES) + 1, FIN_T, 0, stream>>>(dw3p, dzpart, G, (int)dzb, C2, gr->dW3, gr->db3);
     if (Z > 1) {
         const unsigned cb = (unsigned)ceil_div(G * C2, 256);
@@ -959,16 +1017,16 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
         k_zcombine<<<cb, 256, 0, stream>>>(zp3, a->seg_ptr, (int)G, Z, C2, 0, dw3p);
     }
     GSAT_LAUNCH_CHECK();
-    if (!(merged && part_ok) && (rc = colsum(stream, dw3p, G, C2, gr->dW3, scratch))) return rc;
+    if (!merged && (rc = colsum(stream, dw3p, G, C2, gr->dW3, scratch))) return rc;
     if (Z > 1) {
         k_dh2<<<ew_blocks(M * (C2 / 4)), 256, 0, stream>>>(a->h2, a->b2, a->row_seg, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop, a->training,
                                                            a->W3, dz, S1, S2, M, C2, dh2);
         GSAT_LAUNCH_CHECK();
     }
     // dW2[C2,C1] = dh2^T a1 ; da1[M,C1] = dh2 W2
-    if (dual_gemm_ok(1, M, C2, C1, C1)) {            // both products in one pass over dh2 (dual_gemm.hip)
+    if (bp.dual2) {                                  // both products in one pass over dh2 (dual_gemm.hip)
         if ((rc = dual_gemm(stream, 1, M, C2, C1, C1, dh2, C2, a->a1, C1, a->W2, C1, da1, C1, 0, gr->dW2, C1, dws, dws_bytes))) return rc;
-    } else if (pair_ok(M, C2, C1, C1)) {             // both products in one launch, each on its own kernel body (gemm.hip: k_pair_x3)
+    } else if (bp.pair2) {                           // both products in one launch, each on its own kernel body (gemm.hip: k_pair_x3)
         if ((rc = gemm_pair_x3(stream, M, C2, C1, C1, dh2, C2, a->W2, C1, da1, C1, a->a1, C1, gr->dW2, C1, false, gws.ptr, gws.floats, &jobs[0]))) return rc;
     } else {
         if ((rc = gemm_rm(stream, true, false, C2, C1, M, dh2, C2, a->a1, C1, 0.f, gr->dW2, C1, gws, true, &jobs[0]))) return rc;
@@ -1005,7 +1063,7 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
         if ((rc = aggr_sum_fwd_impl(stream, da1, nullptr, nullptr, nullptr, gr->rowptr_dst, gr->eid_by_dst, nullptr, N, M, C1, 0.f, dQ,
                                     gr->chunk_ptr_dst, lpart))) return rc;
         // demb = dP W1a + dQ W1b ; dW1[:, :H] = dP^T emb ; dW1[:, H:] = dQ^T emb
-        if (dual_gemm_ok(2, N, C1, H, H)) {
+        if (bp.dual1) {
             if ((rc = dual_gemm(stream, 2, N, C1, H, H, dP, C1, a->emb, H, a->W1, 2 * H, gr->demb, H, 0, gr->dW1, 2 * H, dws, dws_bytes))) return rc;
             if ((rc = dual_gemm(stream, 2, N, C1, H, H, dQ, C1, a->emb, H, a->W1 + H, 2 * H, gr->demb, H, 1, gr->dW1 + H, 2 * H, dws, dws_bytes))) return rc;
         } else {
@@ -1020,9 +1078,9 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
             k_dh1<false><<<ew_blocks(M * (C1 / 4)), 256, 0, stream>>>(pre, a->row_seg, mean1, rstd1, a->a1, sc, S1p, S2p, M, da1);
             GSAT_LAUNCH_CHECK();
         }
-        if (dual_gemm_ok(2, N, C1, H, H)) {
+        if (bp.dual1) {
             if ((rc = dual_gemm(stream, 2, N, C1, H, H, da1, C1, a->emb, H, a->W1, H, gr->demb, H, 0, gr->dW1, H, dws, dws_bytes))) return rc;
-        } else if (pair_ok(N, C1, H, H)) {
+        } else if (bp.pair1) {
             if ((rc = gemm_pair_x3(stream, N, C1, H, H, da1, C1, a->W1, H, gr->demb, H, a->emb, H, gr->dW1, H, false, gws1.ptr, gws1.floats, &jobs[1]))) return rc;
         } else {
         if ((rc = gemm_rm(stream, false, false, N, H, C1, da1, C1, a->W1, H, 0.f, gr->demb, H, GemmWs{nullptr, 0}, true))) return rc;

@@ -29,10 +29,12 @@ int attn_plan_launch(hipStream_t stream, const int32_t* seg_ptr, const int32_t* 
 bool fused_geometry(int H, int C1, int C2, bool edge, FusedGeom* out, bool pqg = false);
 size_t fused_ws_bytes(const FusedGeom& g, int64_t G);
 bool attn_fused_eligible(const gsat_attn_args* a, FusedGeom* g);
+inline int fused_ncbw(const FusedGeom& g) { return g.NCB2 > 4 ? 2 : 1; }        // 32-column blocks of layer 2 per column wave
 int attn_fused_fwd(hipStream_t stream, const gsat_attn_args* a, const FusedGeom& g);
 
 // fused backward (attn_fused_bwd.hip): (dlogits, datt) -> dh1 [M, C1], dW2, dW3, db3 (db1 = db2 = 0) in one launch + one reduction
 bool attn_fused_bwd_eligible(const gsat_attn_args* a);
+int attn_fused_bwd_ncht(const gsat_attn_args* a);         // layer-1 chunks of the kernel template (2 / 4 / 8); 0: unsupported widths
 size_t attn_fused_bwd_ws_bytes(const gsat_attn_args* a);
 int attn_fused_bwd(hipStream_t stream, const gsat_attn_args* a, const gsat_attn_grads* gr, float* dh1, void* ws, size_t ws_bytes);
 

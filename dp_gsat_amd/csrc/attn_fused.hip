@@ -1068,7 +1068,7 @@ int attn_fused_fwd(hipStream_t stream, const gsat_attn_args* a, const FusedGeom&
     }
     const int grid = (int)std::min<int64_t>(cus, a->G);         // one workgroup per CU pulls tiles from the queue (tiles <= graphs)
     const bool e = a->edge_mode != 0;
-    const int ncbw = g.NCB2 > 4 ? 2 : 1;
+    const int ncbw = fused_ncbw(g);
 #define GO(E, R, W) return launch_fused<E, R, W>(stream, fa, grid)
     if (e && g.pqg) {            // P | Q through global memory: NRB = 2 by construction
         if (g.x6) return launch_fused<true, 2, 1, true, true>(stream, fa, grid);

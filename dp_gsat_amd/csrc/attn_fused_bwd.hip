@@ -648,6 +648,11 @@ bool attn_fused_bwd_eligible(const gsat_attn_args* a) {
     return true;
 }
 
+int attn_fused_bwd_ncht(const gsat_attn_args* a) {
+    BwdGeom g;
+    return bwd_geometry(a->C1, a->C2, &g) ? g.C1pad / B_CH : 0;
+}
+
 size_t attn_fused_bwd_ws_bytes(const gsat_attn_args* a) {
     BwdGeom g;
     if (!bwd_geometry(a->C1, a->C2, &g)) return 0;
@@ -709,7 +714,7 @@ int attn_fused_bwd(hipStream_t stream, const gsat_attn_args* a, const gsat_attn_
     ba.Wq2 = Wq2; ba.dh1 = dh1; ba.partW2 = partW2; ba.partW3 = partW3; ba.partB3 = partB3;
     ba.tiles = tiles; ba.counters = counters; ba.M = a->M; ba.G = a->G;
     ba.seed = SeedRef{a->seed, a->seed_dev}; ba.p = a->p_drop; ba.training = a->training; ba.g = g;
-    const int ncht = g.C1pad / B_CH;
+    const int ncht = attn_fused_bwd_ncht(a);
 #define GO(E, N) rc = launch_bwd<E, N>(stream, ba, nwg)
     if (a->edge_mode) { if (ncht == 2) GO(true, 2); else if (ncht == 4) GO(true, 4); else GO(true, 8); }
     else { if (ncht == 2) GO(false, 2); else if (ncht == 4) GO(false, 4); else GO(false, 8); }

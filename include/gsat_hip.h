@@ -533,6 +533,36 @@ size_t gsat_attn_fwd_workspace_bytes(const gsat_attn_args* args);
 /* which forward gsat_attn_fwd will run for these arguments (host-side, no launch): 0 = staged pipeline (layer products exact fp32 MFMA),
    1 = one-launch forward with exact fp32 MFMA, 2 = one-launch forward with split-bf16 x 6 products.  For logs and benchmark lines. */
 int gsat_attn_fwd_kind(const gsat_attn_args* args);
+/*
+ * Every kernel choice gsat_attn_fwd and gsat_attn_bwd would make for these arguments under the current environment (host-side, no launch,
+ * pointers of `args` are only tested for NULL): writes HOST int32[GSAT_ATTN_PATHS_N], `n` = the slots `out` holds (>= GSAT_ATTN_PATHS_N).
+ * The two entry points branch on the same evaluation of the predicates, so the report cannot drift from the dispatch.  For tests and logs.
+ *   forward:   FWD_KIND as gsat_attn_fwd_kind; for the one-launch forward also FWD_PQG (edge mode: 1 = P | Q of a tile's nodes through
+ *              global memory, 0 = in the tile), FWD_NRB (64-row blocks per row wave: tiles of 64 * NRB rows) and FWD_NCBW (32-column
+ *              blocks of layer 2 per column wave); these three are 0 for the staged pipeline.
+ *   both:      SLICES = row slices per graph of the segmented statistics (1 for batches of small graphs).
+ *   backward:  BWD_FUSED 1 = the one-launch backward down to dh1 (GSAT_ATTN_BWD_FUSED=1 where eligible) with BWD_NCHT layer-1 chunks in
+ *              its template, 0 = staged kernels; BWD_DUAL_L2 / BWD_PAIR_L2 = da1 | dW2 through the dual tile kernel (GSAT_DUAL_GEMM=1) /
+ *              as one gsat_gemm_pair_x3 launch, both 0 = two GEMM calls (also 0 under BWD_FUSED, which forms them itself);
+ *              BWD_DUAL_L1 / BWD_PAIR_L1 = demb | dW1 likewise; BWD_SPLIT 1 = split-bf16 products, 0 = exact fp32 MFMA
+ *              (GSAT_ATTN_BWD_SPLIT=0); BWD_MERGED 1 = dW3 / db3 finished in one launch from the head kernel's partials, 0 = two two-stage
+ *              column sums (GSAT_ATTN_BWD_MERGED=0, sliced segments, or BWD_FUSED).
+ */
+#define GSAT_ATTN_PATH_FWD_KIND 0
+#define GSAT_ATTN_PATH_FWD_PQG 1
+#define GSAT_ATTN_PATH_FWD_NRB 2
+#define GSAT_ATTN_PATH_FWD_NCBW 3
+#define GSAT_ATTN_PATH_SLICES 4
+#define GSAT_ATTN_PATH_BWD_FUSED 5
+#define GSAT_ATTN_PATH_BWD_NCHT 6
+#define GSAT_ATTN_PATH_BWD_DUAL_L2 7
+#define GSAT_ATTN_PATH_BWD_DUAL_L1 8
+#define GSAT_ATTN_PATH_BWD_PAIR_L2 9
+#define GSAT_ATTN_PATH_BWD_PAIR_L1 10
+#define GSAT_ATTN_PATH_BWD_SPLIT 11
+#define GSAT_ATTN_PATH_BWD_MERGED 12
+#define GSAT_ATTN_PATHS_N 13
+int gsat_attn_paths(const gsat_attn_args* args, int32_t* out, int n);
 size_t gsat_attn_bwd_workspace_bytes(const gsat_attn_args* args);
 int gsat_attn_fwd(const gsat_attn_args* args, void* stream);
 int gsat_attn_bwd(const gsat_attn_args* args, const gsat_attn_grads* grads, void* stream);

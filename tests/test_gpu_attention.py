@@ -7,6 +7,8 @@ import torch
 from oracle import bookkeeping as obk
 from oracle import modules as om
 from oracle import ops as oops
+from tests.extractor_cases import CAP_FORWARD, CAP_REGULAR, CAP_TINY_GRAD, MIN_ROWS
+from tests.extractor_oracle import close64
 from tests.graphs import random_batch, shuffle_edges
 from tests.util import close
 
@@ -17,24 +19,42 @@ def _copy_params(dst, src):
     dst.load_state_dict(src.state_dict())
 
 
-@pytest.mark.parametrize("H", [16, 64, 80, 128])
-@pytest.mark.parametrize("edge_mode", [True, False])
-@pytest.mark.parametrize("training", [True, False])
-def test_extractor_fwd_bwd(dev, H, edge_mode, training):
-    import dp_gsat_amd as G
+_GRAD_OF = {f"feature_extractor.{i}.{p}": f"d{'W' if p == 'weight' else 'b'}{n}" for i, n in ((0, 1), (4, 2), (8, 3)) for p in ("weight", "bias")}
+
+
+def _grad_cap(ei, batch, edge_mode, tensor):
+    """The cap on the fp64 comparison's slack term (tests/extractor_cases.py): a batch holding a graph of 1 to 3 rows gets the measured
+    caps of the tiny family, a batch without one the regular cap."""
+    rows = torch.bincount(batch[ei[0]] if edge_mode else batch)
+    return CAP_TINY_GRAD[tensor] if bool(((rows > 0) & (rows < MIN_ROWS)).any()) else CAP_REGULAR
+
+
+FWD_BWD_WEIGHT_SEED = 1000
+MIXED_WEIGHT_SEED = 2000
+
+
+def _seeded_extractor(H, edge_mode, seed):
+    """The reference module with weights drawn from a seed of its own (the process-wide generator stays as it was)."""
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed + H + int(edge_mode))
+        return om.ExtractorMLP(H, edge_mode)
+
+
+def _fwd_bwd_inputs(H, edge_mode):
     ei, batch, N = random_batch(H + 1, 10, 2, 40)
     ei = shuffle_edges(ei, 2)                     # rows of a graph are NOT contiguous -> exercises seg_order
-    E = ei.shape[1]
-    M = E if edge_mode else N
+    M = ei.shape[1] if edge_mode else N
     g = torch.Generator().manual_seed(H)
     emb = torch.randn(N, H, generator=g)
     C1, C2 = (4 * H, H) if edge_mode else (2 * H, H)
     masks = [(torch.rand(M, C1, generator=g) > 0.5).float(), (torch.rand(M, C2, generator=g) > 0.5).float()]
     u = torch.rand(M, 1, generator=g).clamp_(1e-10, 1 - 1e-10)
     gz, ga = torch.randn(M, 1, generator=g), torch.randn(M, 1, generator=g)
+    return ei, batch, emb, masks, u, gz, ga, _seeded_extractor(H, edge_mode, FWD_BWD_WEIGHT_SEED)
 
+
+def _fwd_bwd_refs(H, edge_mode, training, ei, batch, emb, masks, u, gz, ga, oext):
     ref = {}
-    oext = om.ExtractorMLP(H, edge_mode)
     for dt in (torch.float32, torch.float64):
         ext = om.ExtractorMLP(H, edge_mode).to(dt)
         ext.load_state_dict({k: v.to(dt) for k, v in oext.state_dict().items()})
@@ -42,8 +62,21 @@ def test_extractor_fwd_bwd(dev, H, edge_mode, training):
         e = emb.to(dt).clone().requires_grad_(True)
         z = ext(e, ei, batch, masks=[m.to(dt) for m in masks])
         a = oops.concrete_sample(z, u.to(dt), training)
-        torch.autograd.backward([z, a], [gz.to(dt), ga.to(dt)])
+        if gz is not None:
+            torch.autograd.backward([z, a], [gz.to(dt), ga.to(dt)])
+        else:
+            a.backward(ga.to(dt))
         ref[dt] = dict(z=z, a=a, demb=e.grad, **{k: p.grad for k, p in ext.named_parameters()})
+    return ref[torch.float32], ref[torch.float64]
+
+
+@pytest.mark.parametrize("H", [16, 64, 80, 128])
+@pytest.mark.parametrize("edge_mode", [True, False])
+@pytest.mark.parametrize("training", [True, False])
+def test_extractor_fwd_bwd(dev, H, edge_mode, training):
+    import dp_gsat_amd as G
+    ei, batch, emb, masks, u, gz, ga, oext = _fwd_bwd_inputs(H, edge_mode)
+    r32, r64 = _fwd_bwd_refs(H, edge_mode, training, ei, batch, emb, masks, u, gz, ga, oext)
 
     ext = G.ExtractorMLP(H, edge_mode).to(dev)
     ext.load_state_dict(oext.state_dict())
@@ -52,12 +85,12 @@ def test_extractor_fwd_bwd(dev, H, edge_mode, training):
     z, a = ext.attend(ed, ei.to(dev), batch.to(dev), noise=u.to(dev) if training else None,
                       dropout_masks=[m.to(dev) for m in masks])
     torch.autograd.backward([z, a], [gz.to(dev), ga.to(dev)])
-    r32, r64 = ref[torch.float32], ref[torch.float64]
-    close(z, r32["z"], ref64=r64["z"], what="logits")
-    close(a, r32["a"], ref64=r64["a"], what="att")
-    close(ed.grad, r32["demb"], ref64=r64["demb"], what="demb")
+    # fp64 comparisons with the slack term capped: none of them can pass on the reference's own rounding alone
+    close64(z, r32["z"], r64["z"], "logits", CAP_FORWARD)
+    close64(a, r32["a"], r64["a"], "att", CAP_FORWARD)
+    close64(ed.grad, r32["demb"], r64["demb"], "demb", _grad_cap(ei, batch, edge_mode, "demb"))
     for k, p in ext.named_parameters():
-        close(p.grad, r32[k], ref64=r64[k], what=k)
+        close64(p.grad, r32[k], r64[k], k, _grad_cap(ei, batch, edge_mode, _GRAD_OF[k]))
 
 
 def test_extractor_philox_masks_match_explicit(dev):
@@ -213,6 +246,20 @@ def test_extractor_mixed_segment_lengths(dev, H, edge_mode):
     """Batches mixing one-row, short and long (150-210 row) graphs in the unsliced statistics path, also at widths that are not a
     power of two and need several 64-channel column blocks (H = 320: C1 = 640 / 1280)."""
     import dp_gsat_amd as G
+    ei, batch, emb, masks, u, ga, oext = _mixed_inputs(H, edge_mode)
+    r32, r64 = _fwd_bwd_refs(H, edge_mode, True, ei, batch, emb, masks, u, None, ga, oext)
+    ext = G.ExtractorMLP(H, edge_mode).to(dev).train()
+    ext.load_state_dict(oext.state_dict())
+    ed = emb.to(dev).requires_grad_(True)
+    _, a = ext.attend(ed, ei.to(dev), batch.to(dev), noise=u.to(dev), dropout_masks=[m.to(dev) for m in masks])
+    a.backward(ga.to(dev))
+    close64(a, r32["a"], r64["a"], "att", CAP_FORWARD)
+    close64(ed.grad, r32["demb"], r64["demb"], "demb", _grad_cap(ei, batch, edge_mode, "demb"))
+    for k, p in ext.named_parameters():
+        close64(p.grad, r32[k], r64[k], k, _grad_cap(ei, batch, edge_mode, _GRAD_OF[k]))
+
+
+def _mixed_inputs(H, edge_mode):
     from tests.graphs import random_batch as rb
     parts = [rb(7, 30, 2, 14), rb(8, 1, 150, 150), rb(9, 20, 3, 9), rb(10, 1, 210, 210), rb(11, 1, 1, 1)]
     eis, batches, off, goff = [], [], 0, 0
@@ -231,22 +278,4 @@ def test_extractor_mixed_segment_lengths(dev, H, edge_mode):
     masks = [(torch.rand(M, C1, generator=g) > 0.5).float(), (torch.rand(M, C2, generator=g) > 0.5).float()]
     u = torch.rand(M, 1, generator=g).clamp_(1e-10, 1 - 1e-10)
     ga = torch.randn(M, 1, generator=g)
-    oext = om.ExtractorMLP(H, edge_mode)
-    ref = {}
-    for dt in (torch.float32, torch.float64):
-        ext = om.ExtractorMLP(H, edge_mode).to(dt).train()
-        ext.load_state_dict({k: v.to(dt) for k, v in oext.state_dict().items()})
-        e = emb.to(dt).clone().requires_grad_(True)
-        a = oops.concrete_sample(ext(e, ei, batch, masks=[m.to(dt) for m in masks]), u.to(dt), True)
-        a.backward(ga.to(dt))
-        ref[dt] = dict(a=a, demb=e.grad, **{k: p.grad for k, p in ext.named_parameters()})
-    ext = G.ExtractorMLP(H, edge_mode).to(dev).train()
-    ext.load_state_dict(oext.state_dict())
-    ed = emb.to(dev).requires_grad_(True)
-    _, a = ext.attend(ed, ei.to(dev), batch.to(dev), noise=u.to(dev), dropout_masks=[m.to(dev) for m in masks])
-    a.backward(ga.to(dev))
-    r32, r64 = ref[torch.float32], ref[torch.float64]
-    close(a, r32["a"], ref64=r64["a"], what="att")
-    close(ed.grad, r32["demb"], 1e-4, ref64=r64["demb"], what="demb")
-    for k, p in ext.named_parameters():
-        close(p.grad, r32[k], 1e-4, ref64=r64[k], what=k)
+    return ei, batch, emb, masks, u, ga, _seeded_extractor(H, edge_mode, MIXED_WEIGHT_SEED)

@@ -10,33 +10,14 @@ import torch
 
 from oracle import modules as om
 from oracle import ops as oops
+from tests.extractor_cases import sized_batch
 from tests.graphs import random_batch, shuffle_edges
 from tests.util import close
 
 pytestmark = pytest.mark.gpu
 
 
-def _sized_batch(sizes, seed, undirected=True, isolated=True):
-    """Random trees + a few extra edges with the given node counts per graph (0 allowed: an empty graph)."""
-    rng = np.random.RandomState(seed)
-    src, dst, batch, off = [], [], [], 0
-    for g, n in enumerate(sizes):
-        es = set()
-        for v in range(1, n):
-            if isolated and rng.rand() < 0.04:
-                continue
-            es.add((int(rng.randint(0, v)), v))
-        for _ in range(int(0.12 * n)):
-            a, b = rng.randint(0, max(n, 1), size=2)
-            if a != b:
-                es.add((int(min(a, b)), int(max(a, b))))
-        for (u, v) in sorted(es):
-            src += [u + off, v + off] if undirected else [u + off]
-            dst += [v + off, u + off] if undirected else [v + off]
-        batch += [g] * n
-        off += n
-    ei = torch.tensor([src, dst], dtype=torch.int64).reshape(2, -1)
-    return ei, torch.tensor(batch, dtype=torch.int64), off
+_sized_batch = sized_batch
 
 
 def _run(dev, emb, params, ei, batch, G_, edge_mode, training, p, masks, u, fused, seed=7, seed_dev=None):
@@ -206,8 +187,9 @@ def test_fused_extractor_module_vs_oracle_with_big_graph(dev, edge_mode, monkeyp
 
 
 def _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dlogits, datt, fused_bwd, monkeypatch, p=0.5, training=True, seed=7,
-             seed_dev=None, saved=False):
-    """gsat_attn_fwd (staged) + gsat_attn_bwd through the C ABI; returns the gradients and, with ``saved``, also what the forward wrote.
+             seed_dev=None, saved=False, paths=None):
+    """gsat_attn_fwd (staged) + gsat_attn_bwd through the C ABI; returns the gradients and, with ``saved``, also what the forward wrote;
+    a dict given as ``paths`` receives what gsat_attn_paths reports for the backward call.
     Without ``masks`` / ``u`` both passes draw them from ``seed``, or from the device word ``seed_dev`` when given."""
     from dp_gsat_amd import _lib
     from dp_gsat_amd._lib import AttnGrads, call, ptr, stream
@@ -242,6 +224,8 @@ def _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dlogits, datt
     nb = int(_lib.load().gsat_attn_bwd_workspace_bytes(ctypes.byref(args)))
     wsb = torch.empty(nb, dtype=torch.uint8, device=dev)
     g.workspace, g.workspace_bytes = ptr(wsb), nb
+    if paths is not None:
+        paths.update(_lib.attn_paths(args))          # what gsat_attn_bwd is about to run (gsat_attn_paths)
     call("gsat_attn_bwd", ctypes.byref(args), ctypes.byref(g), stream())
     torch.cuda.synchronize()
     out = dict(demb=demb, dW1=grads[0], db1=grads[1], dW2=grads[2], db2=grads[3], dW3=grads[4], db3=grads[5])
@@ -276,8 +260,11 @@ def test_fused_backward_equals_staged_backward(dev, case, H, edge_mode, training
     masks = ((torch.rand(M, C1, generator=g) > 0.5).float().to(dev), (torch.rand(M, C2, generator=g) > 0.5).float().to(dev)) if training else None
     u = torch.rand(M, generator=g).clamp_(1e-6, 1 - 1e-6).to(dev) if training else None
     dl, da = torch.randn(M, generator=g).to(dev), torch.randn(M, generator=g).to(dev)
-    a = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, True, monkeypatch, training=training)
-    b = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, False, monkeypatch, training=training)
+    pa, pb = {}, {}
+    a = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, True, monkeypatch, training=training, paths=pa)
+    b = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, False, monkeypatch, training=training, paths=pb)
+    assert pa["bwd_fused"] == 1 and pa["bwd_ncht"] in (2, 4, 8), pa          # the two runs took the two paths this test names
+    assert pb["bwd_fused"] == 0 and pb["bwd_dual_l2"] == 0 and pb["bwd_dual_l1"] == 0, pb
     for k in a:
         assert not torch.isnan(a[k]).any(), f"{k}: unwritten entries"
         close(a[k], b[k], 1e-4, what=k)          # both paths run the split-bf16 policy; orders of summation differ
@@ -303,10 +290,13 @@ def test_dual_gemm_backward_equals_separate_gemms(dev, case, H, edge_mode, monke
     masks = ((torch.rand(M, C1, generator=g) > 0.5).float().to(dev), (torch.rand(M, C2, generator=g) > 0.5).float().to(dev))
     u = torch.rand(M, generator=g).clamp_(1e-6, 1 - 1e-6).to(dev)
     dl, da = torch.randn(M, generator=g).to(dev), torch.randn(M, generator=g).to(dev)
+    pa, pb = {}, {}
     monkeypatch.setenv("GSAT_DUAL_GEMM", "1")
-    a = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, False, monkeypatch)
+    a = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, False, monkeypatch, paths=pa)
     monkeypatch.setenv("GSAT_DUAL_GEMM", "0")
-    b = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, False, monkeypatch)
+    b = _fwd_bwd(dev, emb, params, ei, batch, G_, edge_mode, masks, u, dl, da, False, monkeypatch, paths=pb)
+    assert (pa["bwd_fused"], pa["bwd_dual_l2"], pa["bwd_dual_l1"]) == (0, 1, 1), pa          # the two runs took the two paths this test names
+    assert (pb["bwd_fused"], pb["bwd_dual_l2"], pb["bwd_dual_l1"]) == (0, 0, 0), pb
     for k in a:
         assert not torch.isnan(a[k]).any(), f"{k}: unwritten entries"
         close(a[k], b[k], 1e-4, what=k)
