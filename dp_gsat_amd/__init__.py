@@ -26,6 +26,8 @@ from .subgraph import StackedExplanationBatch, explanation_fidelity_curve, expla
 from .subgraph import explanation_fidelity_curves, explanation_stack_multi
 from .explain import level_overlap
 from .replay import ReplayedDualFidelityCurve
+from .explain import NodeRanking, node_levels, node_precision_at_k, rank_nodes, topk_node_mask
+from .subgraph import explanation_node_fidelity_curve, explanation_node_subgraph, explanation_stack_nodes
 from .evaluate import (AttentionHistogram, EvaluationMeter, attention_histogram, classifier_accuracy, classifier_rocauc, classifier_rocauc_tasks, pr_curve,
                        task_auroc_counts)
 from .eval_log import EpochLog, FidelityCurveLog, FidelityLog, delta_kl_segments
@@ -42,4 +44,5 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "ReplayedDualEval", "criterion_valid", "PaddedSubgraphBatch", "edge_subgraph_padded", "node_subgraph_padded", "FidelityLog", "ReplayedFidelity",
            "explanation_levels", "StackedExplanationBatch", "explanation_stack", "explanation_fidelity_curve", "FidelityCurveLog",
            "ReplayedFidelityCurve", "explanation_stack_multi", "explanation_fidelity_curves", "level_overlap",
-           "ReplayedDualFidelityCurve"]
+           "ReplayedDualFidelityCurve", "NodeRanking", "rank_nodes", "topk_node_mask", "node_levels", "node_precision_at_k",
+           "explanation_node_subgraph", "explanation_stack_nodes", "explanation_node_fidelity_curve"]

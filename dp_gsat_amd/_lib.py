@@ -153,6 +153,8 @@ SIGNATURES = {
     "gsat_fidelity_stack_multi": (INT, [P, I64, I64, P, I64, P, P, I64, I64, I64, I64, P, P, P, P, P, P, SZ, P]),
     "gsat_level_overlap": (INT, [P, P, I64, I64, P, P, P]),
     "gsat_level_overlap_reset": (INT, [P, I64, P]),
+    "gsat_fidelity_stack_nodes_workspace_bytes": (SZ, [I64, I64, I64]),
+    "gsat_fidelity_stack_nodes": (INT, [P, I64, I64, P, I64, P, P, I64, I64, I64, P, P, P, P, P, P, P, SZ, P]),
 }
 
 

@@ -9,6 +9,9 @@ copied to the host until :meth:`ExplanationMeter.compute`.
 Tie rule (the contract of every ranking here): higher attention first, equal attention -> LOWER EDGE ID first, -0.0 == +0.0.  The
 reference's ``np.argsort(-att)[:k]`` is an unstable sort, i.e. ambiguous under ties -- and ties are the rule in edge-attention mode,
 where the symmetrised mask gives an edge and its reverse the same value.  NaN attention is unsupported.
+
+Node-attention models score nodes: ``rank_nodes`` / ``topk_node_mask`` / ``node_levels`` / ``node_precision_at_k`` run the same kernels on
+the node segments of the batch (``node_ptr``, the identity order, the batch vector), with the same rule: lower NODE id first on ties.
 """
 from __future__ import annotations
 
@@ -19,7 +22,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import GsatHipError, call, ptr, stream
-from .graph_index import call_size, get_index
+from .graph_index import call_size, get_index, sync_free
 
 _PATHS = {"auto": 0, "fused": 1, "general": 2}
 
@@ -72,11 +75,21 @@ def _rank(att, edge_index, batch, num_graphs, path, k=0, label=None, want=("orde
         raise ValueError("max_seg_edges declares a bound for the fused ranking: it does not go with path='general'")
     a = _att(att)
     seg = _segments(edge_index, batch, num_graphs)
-    E, G, dev = seg.index.E, seg.G, a.device
+    E = seg.index.E
     if a.shape[0] != E:
         raise ValueError(f"attention has {a.shape[0]} entries for {E} edges")
     eptr, eorder = seg.edge_segments[:2]
     lab = _labels(label, E) if label is not None else None
+    # -1: the largest graph is unknown and not to be read back now -> general path
+    out = _rank_segments(a, eptr, eorder, seg.G, seg.max_edges_per_graph, path, k, lab, want, max_seg_edges, "max_seg_edges", ranked_graphs)
+    return out, seg
+
+
+def _rank_segments(a, eptr, eorder, G, max_seg, path, k, lab, want, bound, bound_name, ranked_graphs):
+    """The gsat_rank_edges call on generic segments -- the edges of a batch grouped by graph, or its nodes: ``a`` fp32[E] the scores,
+    ``eptr`` int32[G + 1] / ``eorder`` int32[E] the items grouped by graph, ``max_seg`` the largest segment (-1: unknown), ``bound`` the
+    caller's declared bound (named ``bound_name`` in messages) or None.  Returns the dict of the wanted outputs."""
+    E, dev = int(a.shape[0]), a.device
     out = {}
     if "order" in want:
         out["order"] = torch.empty(E, dtype=torch.int32, device=dev)
@@ -86,12 +99,11 @@ def _rank(att, edge_index, batch, num_graphs, path, k=0, label=None, want=("orde
         out["topk"] = torch.empty(E, dtype=torch.uint8, device=dev)
     if "hits" in want:
         out["hits"] = torch.empty(G, dtype=torch.int32, device=dev)
-    max_seg = seg.max_edges_per_graph                      # -1: unknown and not to be read back now -> general path
     code = _PATHS[path]
-    if max_seg_edges is not None:
-        max_seg = int(max_seg_edges)
+    if bound is not None:
+        max_seg = int(bound)
         if not 0 <= max_seg <= rank_edges_lds_cap():
-            raise ValueError(f"max_seg_edges = {max_seg} is outside [0, rank_edges_lds_cap() = {rank_edges_lds_cap()}]: the fused "
+            raise ValueError(f"{bound_name} = {max_seg} is outside [0, rank_edges_lds_cap() = {rank_edges_lds_cap()}]: the fused "
                              "ranking cannot take it, and a declared bound never changes the path silently")
         code = 1
     if ranked_graphs is not None:
@@ -108,7 +120,7 @@ def _rank(att, edge_index, batch, num_graphs, path, k=0, label=None, want=("orde
          ptr(out["hits"]) if "hits" in out and G and lab is not None and E else None, ptr(ws), ws_bytes, stream())
     if "hits" in out and (E == 0 or lab is None):
         out["hits"].zero_()
-    return out, seg
+    return out
 
 
 def rank_edges_lds_cap() -> int:
@@ -250,6 +262,128 @@ def precision_at_k(att, exp_labels, k: int, batch, edge_index, num_graphs: Optio
     return (out["hits"].to(torch.float64) / float(k)).to(torch.float32)
 
 
+# ---- the same ranking over NODES: node-attention models score atoms, superpixels, words ---------------------------------------------------------
+class NodeRanking(NamedTuple):
+    """order int32[N]: node ids graph by graph, best first (``order[node_ptr[g] + r]`` = rank-r node of graph g); rank int32[N]:
+    position of node i inside its graph; node_ptr int32[G+1]."""
+    order: torch.Tensor
+    rank: torch.Tensor
+    node_ptr: torch.Tensor
+
+
+def _node_att(att) -> torch.Tensor:
+    """fp32[N] of a node attention given as [N], [N, 1] or a ``LiftedAttention`` (its ``node_att``, not the lifted product)."""
+    if isinstance(att, ops.LiftedAttention):
+        att = att.node_att
+    if not isinstance(att, torch.Tensor) or not att.is_cuda:
+        raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    if att.dim() > 2 or (att.dim() == 2 and att.shape[1] != 1):
+        raise ValueError("node attention must have shape [N] or [N, 1]")
+    return att.detach().reshape(-1).to(torch.float32).contiguous()
+
+
+def _node_segments(batch, num_graphs):
+    """(node_ptr int32[G + 1], node_graph int32[N], G) of a ``batch`` vector: the segments a batch index has registered for this very
+    tensor (every model forward registers its batch, so a captured body finds them), else one gsat_segment_ptr32 launch."""
+    from .graph_index import _CACHE
+    if not isinstance(batch, torch.Tensor) or not batch.is_cuda:
+        raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    if batch.dtype != torch.int64 or batch.dim() != 1:
+        raise ValueError("batch must be an int64 vector")
+    key = (batch.data_ptr(), batch._version, int(batch.shape[0]))
+    for ix in _CACHE.values():
+        seg = ix._graphs.get(key)
+        if seg is not None and (num_graphs is None or seg.G == int(num_graphs)):
+            return seg.node_ptr, seg.node_seg32, seg.G
+    n = int(batch.shape[0])
+    if num_graphs is None:
+        if sync_free() or torch.cuda.is_current_stream_capturing():
+            raise ValueError("a node ranking of a batch without num_graphs would read batch.max() back")
+        num_graphs = int(batch.max().item()) + 1 if n else 0
+    G, b = int(num_graphs), batch.contiguous()
+    node_ptr = torch.empty(G + 1, dtype=torch.int32, device=b.device)
+    node_graph = torch.empty(max(n, 1), dtype=torch.int32, device=b.device)[:n]
+    flags = torch.zeros(1, dtype=torch.int32, device=b.device)
+    call("gsat_segment_ptr32", ptr(b), n, G, ptr(node_ptr), ptr(node_graph), ptr(flags), stream())
+    return node_ptr, node_graph, G
+
+
+def _rank_n(node_att, batch, num_graphs, path, k=0, label=None, want=("order", "rank"), max_seg_nodes=None, ranked_graphs=None):
+    """:func:`_rank` on the node segments of the batch: ``node_ptr`` as the pointer array, the identity as the order (the nodes of a
+    collated batch are grouped by graph).  Returns (dict of the wanted outputs, node_ptr, node_graph int32[N], G)."""
+    if path not in _PATHS:
+        raise ValueError(f"path must be one of {sorted(_PATHS)}")
+    if ranked_graphs is not None and max_seg_nodes is None:
+        raise ValueError("ranked_graphs is defined on the fused ranking only: give max_seg_nodes (a bound on the nodes of one graph) with it")
+    if max_seg_nodes is not None and _PATHS[path] == 2:
+        raise ValueError("max_seg_nodes declares a bound for the fused ranking: it does not go with path='general'")
+    a = _node_att(node_att)
+    N = int(a.shape[0])
+    if int(batch.shape[0]) != N:
+        raise ValueError(f"node attention has {N} entries for {int(batch.shape[0])} nodes")
+    node_ptr, node_graph, G = _node_segments(batch, num_graphs)
+    max_seg = -1                                           # unknown and not to be read back now -> general path
+    if max_seg_nodes is None and not (sync_free() or torch.cuda.is_current_stream_capturing()):
+        max_seg = int((node_ptr[1:] - node_ptr[:-1]).max().item()) if G > 0 else 0
+    order = torch.arange(N, dtype=torch.int32, device=a.device)
+    lab = _labels(label, N) if label is not None else None
+    out = _rank_segments(a, node_ptr, order, G, max_seg, path, k, lab, want, max_seg_nodes, "max_seg_nodes", ranked_graphs)
+    return out, node_ptr, node_graph, G
+
+
+def rank_nodes(node_att, batch, num_graphs: Optional[int] = None, path: str = "auto") -> NodeRanking:
+    """Every graph's nodes in descending attention order -- the total order of :func:`rank_edges`: higher score first, equal score ->
+    lower node id first, -0.0 == +0.0.  ``node_att``: [N], [N, 1] or a ``LiftedAttention`` (its ``node_att``); ``path`` as in
+    :func:`rank_edges`, the largest graph counted in nodes."""
+    out, node_ptr, _, _ = _rank_n(node_att, batch, num_graphs, path)
+    return NodeRanking(out["order"], out["rank"], node_ptr)
+
+
+def topk_node_mask(node_att, batch, k: Optional[int] = None, ratio: Optional[float] = None, num_graphs: Optional[int] = None,
+                   path: str = "auto", *, max_seg_nodes: Optional[int] = None, ranked_graphs: Optional[int] = None) -> torch.Tensor:
+    """bool[N]: the ``k`` best nodes of every graph, or its ``ceil(ratio * N_g)`` best.  ``max_seg_nodes`` / ``ranked_graphs`` (keyword
+    only) mean for nodes what ``max_seg_edges`` / ``ranked_graphs`` mean in :func:`topk_edge_mask`: a declared bound on the nodes of one
+    graph forces the fused one-launch ranking, also in sync-free mode and under capture (ValueError above ``rank_edges_lds_cap()``), and
+    with ``ranked_graphs`` the rows of the other graphs -- the padding graph of a padded batch -- are NOT written."""
+    if (k is None) == (ratio is None):
+        raise ValueError("give exactly one of k and ratio")
+    bound = dict(max_seg_nodes=max_seg_nodes, ranked_graphs=ranked_graphs)
+    if k is not None:
+        out = _rank_n(node_att, batch, num_graphs, path, k=k, want=("topk",), **bound)[0]
+        return out["topk"].bool()
+    out, node_ptr, node_graph, _ = _rank_n(node_att, batch, num_graphs, path, want=("rank",), **bound)
+    keep = torch.ceil((node_ptr[1:] - node_ptr[:-1]).double() * float(ratio)).to(torch.int32)
+    return out["rank"] < keep[node_graph.long()]
+
+
+def node_levels(node_att, batch, ks=None, ratios=None, num_graphs: Optional[int] = None, *, max_seg_nodes: Optional[int] = None,
+                ranked_graphs: Optional[int] = None) -> torch.Tensor:
+    """uint8[N]: :func:`explanation_levels` over nodes -- for every node the smallest level ``s`` whose top-``ks[s]`` (or
+    top-``ceil(ratios[s] * N_g)``) of its graph holds it, ``len(levels)`` when none does, from ONE ranking: ``node_levels(...) <= s`` is
+    bit for bit ``topk_node_mask(..., k=ks[s] | ratio=ratios[s])``.  A node of a graph that is not ranked gets ``len(levels)``.  Two
+    launches besides the identity order (the ranking and gsat_fidelity_levels), capturable with ``max_seg_nodes``."""
+    ks, ratios = check_levels(ks, ratios)
+    S = len(ks if ks is not None else ratios)
+    out, node_ptr, node_graph, G = _rank_n(node_att, batch, num_graphs, "auto", want=("rank",), max_seg_nodes=max_seg_nodes,
+                                           ranked_graphs=ranked_graphs)
+    N = int(out["rank"].shape[0])
+    level = torch.empty(N, dtype=torch.uint8, device=out["rank"].device)
+    host_ks = (ctypes.c_int64 * S)(*ks) if ks is not None else None
+    host_ratios = (ctypes.c_double * S)(*ratios) if ratios is not None else None
+    call("gsat_fidelity_levels", ptr(out["rank"]) if N else None, ptr(node_ptr), ptr(node_graph) if N else None, N,
+         G if ranked_graphs is None else int(ranked_graphs), host_ks, host_ratios, S, ptr(level) if N else None, stream())
+    return level
+
+
+def node_precision_at_k(node_att, node_label, k: int, batch, num_graphs: Optional[int] = None) -> torch.Tensor:
+    """float32[G] on the device: labelled nodes among each graph's ``k`` best, divided by ``k`` -- also for a graph with fewer than ``k``
+    nodes; the quotient is formed in fp64 and rounded once, like :func:`precision_at_k`."""
+    if int(k) <= 0:
+        raise ValueError("k must be positive")
+    out = _rank_n(node_att, batch, num_graphs, "auto", k=k, label=node_label, want=("hits",))[0]
+    return (out["hits"].to(torch.float64) / float(k)).to(torch.float32)
+
+
 def attention_auroc_counts(att, exp_labels) -> torch.Tensor:
     """int64[3] on the device: (U2, P, Nn) with P / Nn the numbers of labelled / unlabelled edges and
     U2 = sum over labelled edges of (2 * unlabelled edges with lower attention + unlabelled edges with equal attention);
@@ -266,7 +400,9 @@ def attention_auroc_counts(att, exp_labels) -> torch.Tensor:
 
 def attention_auroc(att, exp_labels) -> torch.Tensor:
     """Exact tie-aware ROC-AUC of the attention against binary edge labels: a 0-dim float64 device tensor; 0.0 when only one
-    class is present (src/run_gsat.py:761-763)."""
+    class is present (src/run_gsat.py:761-763).  It scores any vector against labels of the same length: for a node-attention model,
+    ``attention_auroc(node_att, node_label)`` with the [N] or [N, 1] node attention (of a ``LiftedAttention`` its ``.node_att`` -- the
+    object itself stands for the lifted [E, 1] product)."""
     c = attention_auroc_counts(att, exp_labels)
     den = 2 * c[1] * c[2]
     return torch.where(den > 0, c[0].double() / den.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=c.device))

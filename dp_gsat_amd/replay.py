@@ -24,7 +24,7 @@ from .graph_index import clear_cache, get_index, set_sync_free, sync_free
 from .gsat import get_r
 from .ops import edge_tensor
 from .padding import padded
-from .subgraph import edge_subgraph_padded, explanation_stack, explanation_stack_multi
+from .subgraph import edge_subgraph_padded, explanation_stack, explanation_stack_multi, explanation_stack_nodes
 
 _MULTI_LABEL = "a padded batch cannot take the multi-label criterion (its boolean indexing is not capturable)"
 _MULTI_LABEL_HINT = _MULTI_LABEL + "; construct it as Criterion(num_class, True, capturable=True)"
@@ -938,27 +938,51 @@ class ReplayedFidelityCurve(_Replayed):
 
     Multi-task models (``Criterion(T, True, capturable=True)``): the log is a ``FidelityCurveLog(..., tasks=T)`` -- every (graph, task) is
     a binary decision of its own -- and ``run`` adds ``fidelity_plus_tasks``, ``fidelity_minus_tasks``, ``p_keep_tasks``, ``p_drop_tasks``,
-    ``flip_plus_tasks``, ``flip_minus_tasks`` (``[S][T]``) and ``p_full_tasks`` (``[T]``); the per-level keys are the means over the tasks."""
+    ``flip_plus_tasks``, ``flip_minus_tasks`` (``[S][T]``) and ``p_full_tasks`` (``[T]``); the per-level keys are the means over the tasks.
+
+    ``unit="edge"`` (the default) is all of the above.  ``unit="node"`` is the curve over NODES for a node-attention model
+    (``learn_edge_att=False``): a replay ranks ``forward_pass(...)[0].node_att`` inside every graph (``node_levels``, the fused ranking with
+    the dataset's largest node count as its bound), stacks the ``2 S + 1`` node-induced variants with ``explanation_stack_nodes`` -- a
+    variant deletes node rows, relabels its endpoints and keeps an edge only when both ends survive --, runs the one ``clf`` forward and
+    appends to the same ``FidelityCurveLog`` (multi-task ``tasks=T`` included).  It publishes ``node_att`` [N_cap, 1], ``node_level``
+    uint8[N_cap], ``stack``, ``logits`` and ``batch``.  ``run`` adds ``kept_node_fraction``, per level the kept nodes over the nodes of the
+    graphs ``graph_ids``: computed on the host from the dataset's node counts and the level rule (``min(k, N_g)``, or the same fp64
+    ``ceil(N_g * ratio)``), exact, with no device read per batch; ``kept_fraction`` stays the fraction of edges.  Refused besides the above:
+    a model that learns edge attention, and a dataset whose largest graph has more NODES than ``rank_edges_lds_cap()`` (its edge counts
+    are not ranked and not bounded)."""
 
     def __init__(self, gsat, dataset, batch_size: int, ks=None, ratios=None, capacity: Optional[tuple] = None,
-                 max_graphs: Optional[int] = None, graph=None, ragged: bool = False):
+                 max_graphs: Optional[int] = None, graph=None, ragged: bool = False, unit: str = "edge"):
         self.ks, self.ratios = _explain.check_levels(ks, ratios)
+        if unit not in ("edge", "node"):
+            raise ValueError("unit must be 'edge' or 'node'")
+        self.unit = unit
         if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
             raise ValueError("ReplayedFidelityCurve replays GSAT.forward_pass and its backbone; DualGSAT fidelity is not covered")
+        if unit == "node" and gsat.learn_edge_att:
+            raise ValueError("ReplayedFidelityCurve(unit='node') ranks the node attention of a node-attention model (learn_edge_att=False); "
+                             "this model learns edge attention: use unit='edge'")
         _refuse_uncapturable(gsat.criterion)
         _refuse_sync_group(gsat)
         if dataset.y_all is None:
             raise ValueError("ReplayedFidelityCurve needs a dataset with graph labels (the eval-mode forward takes them); edge labels are "
                              "not needed")
-        self.max_seg_edges = int(dataset.edge_counts.max()) if dataset.num_graphs else 0          # one host read, here
-        if self.max_seg_edges > _explain.rank_edges_lds_cap():
-            raise ValueError(f"the dataset's largest graph has {self.max_seg_edges} edges, above rank_edges_lds_cap() = "
-                             f"{_explain.rank_edges_lds_cap()}: the captured ranking takes the fused path only")
+        if unit == "node":
+            self._host_nodes = dataset.node_counts.cpu().numpy().astype("int64")                   # one host read, here
+            self.max_seg_nodes = int(self._host_nodes.max()) if dataset.num_graphs else 0
+            if self.max_seg_nodes > _explain.rank_edges_lds_cap():
+                raise ValueError(f"the dataset's largest graph has {self.max_seg_nodes} nodes, above rank_edges_lds_cap() = "
+                                 f"{_explain.rank_edges_lds_cap()}: the captured ranking takes the fused path only")
+        else:
+            self.max_seg_edges = int(dataset.edge_counts.max()) if dataset.num_graphs else 0      # one host read, here
+            if self.max_seg_edges > _explain.rank_edges_lds_cap():
+                raise ValueError(f"the dataset's largest graph has {self.max_seg_edges} edges, above rank_edges_lds_cap() = "
+                                 f"{_explain.rank_edges_lds_cap()}: the captured ranking takes the fused path only")
         self.gsat, self.dataset = gsat, dataset
         self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
         self._max_graphs = dataset.num_graphs if max_graphs is None else int(max_graphs)
         self._overflow = torch.zeros(1, dtype=torch.int32, device=dataset.x_all.device)
-        self.log = self.batch = self.edge_att = self.edge_level = self.stack = self.logits = None
+        self.log = self.batch = self.edge_att = self.edge_level = self.node_att = self.node_level = self.stack = self.logits = None
         try:
             _capture_evaluator(self, self._make_log)
         finally:
@@ -976,9 +1000,15 @@ class ReplayedFidelityCurve(_Replayed):
         """Attention, levels, the stack, the one backbone forward and the append for batch ``b`` -- a ``PaddedBatch`` (the captured body)
         or ``collate`` output (the eager tail, stacked at the captured batch size); the modules are in eval mode."""
         with torch.no_grad():
-            att = edge_tensor(self.gsat.forward_pass(b, epoch, False)[0]).detach()
+            att = self.gsat.forward_pass(b, epoch, False)[0]
             valid = getattr(b, "valid", None)
-            stack = explanation_stack(b, att, ks=self.ks, ratios=self.ratios, batch_size=self.batch_size, max_seg_edges=self.max_seg_edges)
+            if self.unit == "node":
+                att = att.node_att.detach()
+                stack = explanation_stack_nodes(b, att, ks=self.ks, ratios=self.ratios, batch_size=self.batch_size,
+                                                max_seg_nodes=self.max_seg_nodes)
+            else:
+                att = edge_tensor(att).detach()
+                stack = explanation_stack(b, att, ks=self.ks, ratios=self.ratios, batch_size=self.batch_size, max_seg_edges=self.max_seg_edges)
             logits = self.gsat.clf(stack.x, stack.edge_index, stack.batch, stack.edge_attr)
             over = stack.valid[:, 3].amax().view(1)
             self._overflow.bitwise_or_(over if valid is None else over | valid[3:4])
@@ -991,13 +1021,32 @@ class ReplayedFidelityCurve(_Replayed):
         b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
         b.r = self.r
         att, stack, logits = self._forward(b, 0)
-        self._publish(False, batch=b, edge_att=att, edge_level=stack.edge_level, stack=stack, logits=logits)
+        if self.unit == "node":
+            self._publish(False, batch=b, node_att=att, node_level=stack.node_level, stack=stack, logits=logits)
+        else:
+            self._publish(False, batch=b, edge_att=att, edge_level=stack.edge_level, stack=stack, logits=logits)
 
     def run(self, graph_ids, epoch: int = 0) -> dict:
         """One curve epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, a
         fixed-count tail of fewer than ``batch_size`` graphs runs eagerly through the same code, and ``log.compute()`` -- one reduction
-        launch, one host read -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
-        return _run_epoch(self, graph_ids, epoch)
+        launch, one host read -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a replay.
+        ``unit="node"`` adds ``kept_node_fraction`` (see the class)."""
+        res = _run_epoch(self, graph_ids, epoch)
+        if self.unit == "node":
+            res["kept_node_fraction"] = self._kept_node_fraction(graph_ids)
+        return res
+
+    def _kept_node_fraction(self, graph_ids) -> list:
+        """Per level, kept nodes / nodes over the graphs ``graph_ids``, on the host: the level rule of ``node_levels`` -- ``min(k, N_g)`` or
+        the fp64 ``ceil(N_g * ratio)`` -- on the dataset's node counts, in integers."""
+        import numpy as np
+        n = self._host_nodes[torch.as_tensor(graph_ids).reshape(-1).cpu().numpy().astype(np.int64)]
+        total = int(n.sum())
+        if self.ks is not None:
+            kept = [int(np.minimum(n, k).sum()) for k in self.ks]
+        else:
+            kept = [int(np.ceil(n.astype(np.float64) * r).astype(np.int64).sum()) for r in self.ratios]
+        return [k / total if total else 0.0 for k in kept]
 
     def overflowed(self) -> bool:
         """True if a batch or a variant of its stack since the last call (or since capture) did not fit its capacity.  One host read;

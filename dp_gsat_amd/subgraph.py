@@ -360,7 +360,10 @@ class StackedExplanationBatch(Batch):
     (host ints: variant ``v`` owns the edge slots ``[segment_offsets[v], segment_offsets[v + 1])``), ``node_capacity`` (variant ``v`` owns
     the node rows ``[v * node_capacity, (v + 1) * node_capacity)``), ``graphs_per_variant`` (the padding graph last), ``edge_id``
     (int64[E_stack]: the input's edge slot, -1 for padding) and ``edge_level`` (uint8[E]: :func:`explanation_levels` of the input).
-    ``rankings`` is 1; of :func:`explanation_stack_multi` it is ``R``, with ``variants = 1 + 2 R S`` and ``edge_level`` uint8[R, E]."""
+    ``rankings`` is 1; of :func:`explanation_stack_multi` it is ``R``, with ``variants = 1 + 2 R S`` and ``edge_level`` uint8[R, E].
+    Of :func:`explanation_stack_nodes` the variants are node-induced: ``valid[v, 0]`` is the variant's own node count, and in place of
+    ``edge_level`` the batch carries ``node_id`` (int64[variants * node_capacity]: the input's row, -1 for padding), ``node_level``
+    (uint8[N]) and the gathered ``node_label``."""
 
     def check(self) -> "StackedExplanationBatch":
         """One host read of ``valid``: raises ValueError when a variant overflowed (it is then all padding)."""
@@ -508,16 +511,14 @@ def _explanation_stack(data, atts, ks, ratios, batch_size, max_seg_edges, edge_l
     return stack
 
 
-def explanation_fidelity_curve(clf, data, att, ks=None, ratios=None) -> dict:
-    """The fidelity curve of the explanation ``att`` for the backbone ``clf`` over the levels ``ks`` or ``ratios``: eval mode, no grad,
-    :func:`explanation_stack`, ONE ``clf`` forward WITHOUT ``edge_atten`` on the stack.  Returns what ``FidelityCurveLog.compute()``
-    returns, as fp64 device tensors -- ``fidelity_plus`` / ``fidelity_minus`` / ``p_keep`` / ``p_drop`` / ``flip_plus`` / ``flip_minus`` /
-    ``kept_fraction`` of shape [S], ``p_full`` and ``n`` 0-dim -- with ``levels`` and the stacked ``logits [V, graphs_per_variant, C]``."""
+def _stack_curve(clf, make_stack) -> dict:
+    """Eval mode, no grad: ``stack = make_stack()``, ONE ``clf`` forward WITHOUT ``edge_atten`` on it, and the scores of
+    :func:`explanation_fidelity_curve` as fp64 device tensors, plus ``stack``."""
     was_training = clf.training
     clf.eval()
     try:
         with torch.no_grad():
-            stack = explanation_stack(data, att, ks=ks, ratios=ratios)
+            stack = make_stack()
             S, V, Gp = len(stack.levels), stack.variants, stack.graphs_per_variant
             logits = clf(stack.x, stack.edge_index, stack.batch, stack.edge_attr).view(V, Gp, -1)
             z = logits.double()
@@ -536,7 +537,17 @@ def explanation_fidelity_curve(clf, data, att, ks=None, ratios=None) -> dict:
         clf.train(was_training)
     return {"levels": stack.levels, "fidelity_plus": mean(p[0] - p[1 + S:]), "fidelity_minus": mean(p[0] - p[1:1 + S]), "p_full": mean(p[0]),
             "p_keep": mean(p[1:1 + S]), "p_drop": mean(p[1 + S:]), "flip_plus": flips[1 + S:], "flip_minus": flips[1:1 + S],
-            "kept_fraction": kept[1:1 + S] / kept[0], "n": n, "logits": logits}
+            "kept_fraction": kept[1:1 + S] / kept[0], "n": n, "logits": logits, "stack": stack}
+
+
+def explanation_fidelity_curve(clf, data, att, ks=None, ratios=None) -> dict:
+    """The fidelity curve of the explanation ``att`` for the backbone ``clf`` over the levels ``ks`` or ``ratios``: eval mode, no grad,
+    :func:`explanation_stack`, ONE ``clf`` forward WITHOUT ``edge_atten`` on the stack.  Returns what ``FidelityCurveLog.compute()``
+    returns, as fp64 device tensors -- ``fidelity_plus`` / ``fidelity_minus`` / ``p_keep`` / ``p_drop`` / ``flip_plus`` / ``flip_minus`` /
+    ``kept_fraction`` of shape [S], ``p_full`` and ``n`` 0-dim -- with ``levels`` and the stacked ``logits [V, graphs_per_variant, C]``."""
+    res = _stack_curve(clf, lambda: explanation_stack(data, att, ks=ks, ratios=ratios))
+    del res["stack"]
+    return res
 
 
 def explanation_fidelity_curves(clf, data, atts, ks=None, ratios=None, *, batch_size: Optional[int] = None,
@@ -580,3 +591,130 @@ def explanation_fidelity_curves(clf, data, atts, ks=None, ratios=None, *, batch_
     finally:
         clf.train(was_training)
     return out
+
+
+# ---- node explanations: top-k node subgraphs, the node-induced stack, its fidelity curve -------------------------------------------------------
+def _node_scores(node_att, N: int) -> torch.Tensor:
+    a = node_att.node_att if isinstance(node_att, ops.LiftedAttention) else node_att
+    if not isinstance(a, torch.Tensor) or a.numel() != N:
+        raise ValueError(f"node attention must have one entry for each of the {N} nodes")
+    return a
+
+
+def explanation_node_subgraph(node_att, data, k: Optional[int] = None, ratio: Optional[float] = None, complement: bool = False) -> SubgraphBatch:
+    """Every graph's ``k`` (or ``ceil(ratio * N_g)``) highest-attention NODES and the edges among them as a batch of their own
+    (``complement``: everything BUT those nodes): :func:`node_subgraph` on :func:`~dp_gsat_amd.explain.topk_node_mask`; ties as in
+    :mod:`dp_gsat_amd.explain` (lower node id first).  The kept nodes' attention rides along as ``node_att = node_att[node_id]``."""
+    from .explain import topk_node_mask
+    if (k is None) == (ratio is None):
+        raise ValueError("give exactly one of k and ratio")
+    a = _node_scores(node_att, int(data.x.shape[0]))
+    _need_cuda(a, data.edge_index, data.batch, data.x)
+    mask = topk_node_mask(a, data.batch, k=k, ratio=ratio, num_graphs=getattr(data, "num_graphs", None))
+    if complement:
+        mask = ~mask
+    sub = node_subgraph(data, mask)
+    sub.node_att = gather_rows(a.detach().contiguous(), sub.node_id)
+    return sub
+
+
+def explanation_stack_nodes(data, node_att, ks=None, ratios=None, batch_size: Optional[int] = None, *, max_seg_nodes: Optional[int] = None,
+                            node_level: Optional[torch.Tensor] = None) -> StackedExplanationBatch:
+    """:func:`explanation_stack` for a NODE explanation (gsat_fidelity_stack_nodes): with ``S`` levels the ``V = 2 S + 1`` node-induced
+    variants "the batch itself", "the nodes of level s alone" (``v = 1 + s``) and "the batch without them" (``v = 1 + S + s``) side by
+    side, so that ONE backbone forward scores a whole node-fidelity curve.  A variant deletes rows -- which is what changes sum / mean
+    pools and PNA degrees --, relabels its endpoints and keeps an edge only when both ends survive; it holds, inside its node rows, graph
+    ids and edge segment, bit for bit what ``node_subgraph_padded(data, mask_v, (node_capacity, E))`` holds.
+
+    ``data``: a ``Batch`` of ``G`` graphs (``graphs_per_variant = G + 1``, ``node_capacity = N + 2``) or a ``PaddedBatch`` (its own
+    ``num_graphs`` and node rows), the node capacity of ``explanation_stack``.  Every variant's edge segment is ``E``: the levels bound
+    the kept NODES of a graph, and a node-induced subgraph has no bound below ``E`` that they imply (a top-1 node with self loops keeps
+    them all), so ``batch_size`` changes nothing here and is accepted for symmetry only.  ``x`` and ``node_label`` are gathered by
+    ``node_id`` and ``edge_attr`` by ``edge_id``, with zero rows in the padding; the result also carries ``node_id`` (int64[V *
+    node_capacity], the input's row, -1 for padding) and ``node_level`` (uint8[N]: :func:`~dp_gsat_amd.explain.node_levels` of the input).
+
+    ``max_seg_nodes``: the bound that keeps the ranking on the fused path (needed in sync-free mode and under capture); ``node_level``:
+    levels computed before, in place of ``node_att``.  Five launches for the stack whatever ``S`` is, nothing read back: capturable.
+    Overflow is per variant; an overflowed input or a bad node id spoils all: a ValueError after one host read of ``valid[:, 3]`` -- in
+    sync-free mode or under capture nothing is read and ``.check()`` reports it."""
+    from .explain import check_levels, node_levels
+    ks, ratios = check_levels(ks, ratios)
+    levels = ks if ks is not None else ratios
+    S = len(levels)
+    V = 2 * S + 1
+    x, edge_index, batch = data.x, data.edge_index, data.batch
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    N, E, dev = int(x.shape[0]), int(edge_index.shape[1]), edge_index.device
+    if batch.dtype != torch.int64 or batch.dim() != 1 or int(batch.shape[0]) != N:
+        raise ValueError("batch must be an int64 vector with one entry per node")
+    _need_cuda(x, edge_index, batch, node_level)
+    capturing = torch.cuda.is_current_stream_capturing()
+    valid_in = getattr(data, "valid", None)
+    if valid_in is not None:
+        if valid_in.dtype != torch.int32 or valid_in.numel() < 4 or not valid_in.is_cuda:
+            raise ValueError("data.valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+        valid_in = valid_in.contiguous()
+        Gp = int(data.num_graphs)
+        real, N_cap = Gp - 1, N
+        if N_cap < 2:
+            raise ValueError("a padded batch has at least two node rows (the padding nodes)")
+    else:
+        real = getattr(data, "num_graphs", None)
+        if real is None:
+            if sync_free() or capturing:
+                raise ValueError("a stack of a batch without num_graphs would read batch.max() back")
+            real = int(batch.max().item()) + 1 if N else 0
+        real = int(real)
+        Gp, N_cap = real + 1, N + 2
+    ei, batch = edge_index.contiguous(), batch.contiguous()
+    if node_level is None:
+        a = _node_scores(node_att, N)
+        node_level = node_levels(a, batch, ks=ks, ratios=ratios, num_graphs=Gp if valid_in is not None else real,
+                                 max_seg_nodes=max_seg_nodes, ranked_graphs=real if max_seg_nodes is not None else None)
+    else:
+        if node_level.dtype != torch.uint8 or node_level.numel() != N:
+            raise ValueError(f"node_level must be a uint8 tensor with one entry for each of the {N} nodes")
+        node_level = node_level.reshape(-1).contiguous()
+    offsets = [v * E for v in range(V + 1)]
+    E_stack = offsets[-1]
+    ws_bytes = max(call_size("gsat_fidelity_stack_nodes_workspace_bytes", N, E, S), 256)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    new_ei = torch.empty(2, E_stack, dtype=torch.int64, device=dev)
+    edge_id = torch.empty(E_stack, dtype=torch.int64, device=dev)
+    node_id = torch.empty(V * N_cap, dtype=torch.int64, device=dev)
+    new_batch = torch.empty(V * N_cap, dtype=torch.int64, device=dev)
+    valid = torch.empty(V, 4, dtype=torch.int32, device=dev)
+    some = lambda t: ptr(t) if t is not None and t.numel() else None
+    call("gsat_fidelity_stack_nodes", some(ei), E, N, some(batch), real, ptr(valid_in) if valid_in is not None else None, some(node_level), S,
+         Gp, N_cap, (ctypes.c_int64 * (V + 1))(*offsets), some(new_ei), some(edge_id), ptr(node_id), ptr(new_batch), ptr(valid), ptr(ws),
+         ws_bytes, stream())
+    if not (sync_free() or capturing) and int(valid[:, 3].any()):                                   # the one host read
+        raise ValueError(_overflow_text((N_cap, (E,) * V)))
+    gathered = {}
+    for name, index, rows in (("edge_attr", edge_id, E), ("node_label", node_id, N)):
+        t = getattr(data, name, None)
+        if isinstance(t, torch.Tensor):
+            _need_cuda(t)
+            if int(t.shape[0]) != rows:
+                raise ValueError(f"{name} has {t.shape[0]} rows")
+            t = _take_padded(t, index)
+        gathered[name] = t
+    stack = StackedExplanationBatch(x=_take_padded(x, node_id), edge_index=new_ei, batch=new_batch, y=getattr(data, "y", None),
+                                    num_graphs=V * Gp, valid=valid, levels=tuple(levels), by_ratio=ratios is not None, variants=V,
+                                    segment_offsets=tuple(offsets), node_capacity=N_cap, graphs_per_variant=Gp, edge_id=edge_id,
+                                    node_id=node_id, node_level=node_level, rankings=1, **gathered)
+    # a backbone forward on the stack then returns num_graphs rows and never reads batch.max() back
+    get_index(new_ei, V * N_cap).graphs(new_batch, V * Gp)
+    return stack
+
+
+def explanation_node_fidelity_curve(clf, data, node_att, ks=None, ratios=None) -> dict:
+    """:func:`explanation_fidelity_curve` for a NODE explanation: eval mode, no grad, :func:`explanation_stack_nodes`, ONE ``clf`` forward
+    WITHOUT ``edge_atten`` on the stack.  The same keys as fp64 device tensors -- ``kept_fraction`` stays the fraction of EDGES a keep
+    variant holds -- plus ``kept_node_fraction`` [S] (``valid[1:1 + S, 0] / valid[0, 0]``)."""
+    res = _stack_curve(clf, lambda: explanation_stack_nodes(data, node_att, ks=ks, ratios=ratios))
+    valid = res.pop("stack").valid
+    kept = valid[:, 0].double()
+    res["kept_node_fraction"] = kept[1:len(res["levels"]) + 1] / kept[0]
+    return res

@@ -31,12 +31,18 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
     the top-ratio explanation on the test split at every ratio (``dp_gsat_amd.ReplayedFidelityCurve``).  One captured graph ranks the
     edges once, stacks the batch, every explanation and every complement into ONE batch and runs the backbone once.
 
+  * ``--node-attention`` -- the extractor scores nodes (``learn_edge_att=False``); the edge attention is the lifted product.  With it,
+    ``--fidelity-curve ... --fidelity-unit node`` ranks the NODES: every level keeps (or removes) the top-ratio nodes of each graph and
+    the edges among them, and each level line also shows the fraction of nodes kept.  The class refuses ``--fidelity-unit node`` for a
+    model that learns edge attention, and the example passes that refusal through.
+
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --train-scores
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity 5
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity-curve 0.2,0.5,0.8
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --node-attention --fidelity-curve 0.2,0.5,0.8 --fidelity-unit node
 """
 import argparse
 import os
@@ -93,6 +99,9 @@ def main():
     ap.add_argument("--fidelity", type=int, default=None, metavar="K", help="with --graph: print the fidelity of the top-K explanation on the test split")
     ap.add_argument("--fidelity-curve", type=lambda s: [float(v) for v in s.split(",")], default=None, metavar="R1,R2,...",
                     help="with --graph: print the fidelity of the top-ratio explanation on the test split at every ratio (increasing, in (0, 1])")
+    ap.add_argument("--fidelity-unit", default="edge", choices=["edge", "node"],
+                    help="with --fidelity-curve: rank and remove edges, or the nodes of a --node-attention model")
+    ap.add_argument("--node-attention", action="store_true", help="learn node attention (learn_edge_att=False) instead of edge attention")
     args = ap.parse_args()
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -126,10 +135,10 @@ def main():
     cfg = dict(model_name=args.backbone, n_layers=2, hidden_size=args.hidden, dropout_p=0.3, use_edge_attr=False,
                aggregators=["mean", "min", "max", "std", "sum"], scalers=False, deg=deg)
     clf = G.get_model(10, 0, 2, False, cfg, dev)
-    ext = G.ExtractorMLP(args.hidden, True).to(dev)
+    ext = G.ExtractorMLP(args.hidden, not args.node_attention).to(dev)
     params = list(clf.parameters()) + list(ext.parameters())
     opt = torch.optim.Adam(params, lr=1e-3, weight_decay=3e-6, **(dict(capturable=True, fused=True) if args.graph else {}))
-    gsat = G.GSAT(clf, ext, G.Criterion(2, False), opt, learn_edge_att=True)
+    gsat = G.GSAT(clf, ext, G.Criterion(2, False), opt, learn_edge_att=not args.node_attention)
     flat = FlatGradAllReduce(params) if world > 1 else None
     torch.manual_seed(args.seed + 1000 * rank)                    # independent noise / dropout per rank from here on
 
@@ -157,7 +166,8 @@ def main():
         if args.fidelity is not None:
             replayed_fidelity = G.ReplayedFidelity(gsat, ds, slots, k=args.fidelity, capacity=capacity, ragged=True)
         if args.fidelity_curve is not None:
-            replayed_curve = G.ReplayedFidelityCurve(gsat, ds, slots, ratios=args.fidelity_curve, capacity=capacity, ragged=True)
+            replayed_curve = G.ReplayedFidelityCurve(gsat, ds, slots, ratios=args.fidelity_curve, capacity=capacity, ragged=True,
+                                                     unit=args.fidelity_unit)
     elif args.graph and n_train >= args.batch_size:
         replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
     if args.graph and not args.ragged:
@@ -165,7 +175,8 @@ def main():
         if args.fidelity is not None:
             replayed_fidelity = G.ReplayedFidelity(gsat, ds, min(args.batch_size, len(graphs)), k=args.fidelity)
         if args.fidelity_curve is not None:
-            replayed_curve = G.ReplayedFidelityCurve(gsat, ds, min(args.batch_size, len(graphs)), ratios=args.fidelity_curve)
+            replayed_curve = G.ReplayedFidelityCurve(gsat, ds, min(args.batch_size, len(graphs)), ratios=args.fidelity_curve,
+                                                     unit=args.fidelity_unit)
 
     def evaluate_replayed(ids, epoch):
         res = replayed_eval.run(ids, epoch)      # full batches: replays; the tail: eager (--ragged: a replay too); one scoring pass at the end
@@ -213,7 +224,8 @@ def main():
             if replayed_curve is not None:                        # every level from ONE ranking and ONE backbone forward per batch
                 res = replayed_curve.run(test_ids)
                 for s, ratio in enumerate(res["levels"]):
-                    print(f"      fidelity@{ratio:g}  kept {res['kept_fraction'][s]:.3f}  fidelity_plus {res['fidelity_plus'][s]:.4f}  "
+                    nodes = f"  kept nodes {res['kept_node_fraction'][s]:.3f}" if args.fidelity_unit == "node" else ""
+                    print(f"      fidelity@{ratio:g}  kept {res['kept_fraction'][s]:.3f}{nodes}  fidelity_plus {res['fidelity_plus'][s]:.4f}  "
                           f"fidelity_minus {res['fidelity_minus'][s]:.4f}  flip_plus {res['flip_plus'][s]:.3f}  "
                           f"flip_minus {res['flip_minus'][s]:.3f}", flush=True)
             if args.train_scores:                                 # scored from what the replays of this epoch logged: no eager batch

@@ -1170,6 +1170,39 @@ int gsat_level_overlap(const uint8_t* level_a, const uint8_t* level_b, int64_t E
 /* acc int64[levels, 3] = 0, by a kernel (no memset node). */
 int gsat_level_overlap_reset(int64_t* acc, int64_t levels, void* stream);
 
+/*
+ * gsat_fidelity_stack over NODES: the V = 2 * levels + 1 padded node-induced extractions of a fidelity curve side by side.  node_level
+ * uint8[N] is what gsat_fidelity_levels writes for a ranking of the nodes inside their graphs (values above `levels` count as
+ * `levels`).  Variant 0 keeps every real node, variant 1 + s the real nodes with level <= s, variant 1 + levels + s those with level > s.
+ * A row at or beyond valid_in[0] is never kept and its level byte is never read; an edge slot at or beyond valid_in[1] is never read.
+ * Variant v owns the node rows [v * cap_nodes, (v + 1) * cap_nodes), the graph ids [v * graphs_per_variant, (v + 1) *
+ * graphs_per_variant) with the padding graph last, and the edge slots [segment_offsets[v], segment_offsets[v + 1]); segment_offsets
+ * int64[V + 1] in HOST memory, starting at 0, non-decreasing; E_stack = segment_offsets[V].  Inside them it holds, bit for bit, what
+ * gsat_subgraph_padded writes with mode = 1, drop_isolated = 0, the variant's keep mask, the same valid_in, pad_graph =
+ * graphs_per_variant - 1 and the capacity (cap_nodes, segment length) -- the node ids of out_edge_index moved by v * cap_nodes and
+ * out_batch by v * graphs_per_variant:
+ *   out_node_id int64[V * cap_nodes]  kept nodes in ascending old order, -1 for padding rows
+ *   out_batch int64[V * cap_nodes]    the graph of every kept node, the variant's padding graph for the rest
+ *   out_edge_index int64[2, E_stack], out_edge_id int64[E_stack]   the edges with BOTH ends kept, in their order, relabelled, and their
+ *                                     slots in the input; then the slack as padding edges among the variant's padding nodes, id -1
+ *   valid_out int32[V, 4]             (N'_v, E'_v, graphs, 0)
+ * An isolated kept node stays; a graph that lost every node is an empty segment.  Overflow is PER VARIANT (N'_v differs): a variant with
+ * N'_v + 2 > cap_nodes or more kept edges than its segment is all padding with (0, 0, 0, 1) and the others stand; valid_in[3] != 0 or
+ * a counted edge with an endpoint outside [0, N_real) makes every variant all padding.  Nothing is written out of bounds.
+ * 5 launches whatever `levels` is (per-workgroup counts of the nodes' bins and of the edges' max / min endpoint bins; one workgroup
+ * scans them; node scatter with a per-node prefix table int32[N, levels + 1] in the workspace; edge scatter; fill), kernels only, no
+ * atomics, nothing read back: capturable and bitwise repeatable.  Each workgroup owns gsat_fidelity_stack_block_items() node rows or
+ * edge slots.  1 <= levels <= 16 and cap_nodes >= 2 (GSAT_ERR_ARG otherwise); every extent, V * cap_nodes and V * graphs_per_variant
+ * < 2^31 (GSAT_ERR_UNSUPPORTED otherwise).  workspace: gsat_fidelity_stack_nodes_workspace_bytes(N, E, levels) (0 for arguments out of
+ * range).
+ * replaces: 2 * levels calls of gsat_subgraph_padded in node mode (5 launches each) and as many backbone forwards by one stacked forward.
+ */
+size_t gsat_fidelity_stack_nodes_workspace_bytes(int64_t N, int64_t E, int64_t levels);
+int gsat_fidelity_stack_nodes(const int64_t* edge_index, int64_t E, int64_t N, const int64_t* batch, int64_t G, const int32_t* valid_in,
+                              const uint8_t* node_level, int64_t levels, int64_t graphs_per_variant, int64_t cap_nodes,
+                              const int64_t* segment_offsets, int64_t* out_edge_index, int64_t* out_edge_id, int64_t* out_node_id,
+                              int64_t* out_batch, int32_t* valid_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
