@@ -81,6 +81,12 @@ SIGNATURES = {
     "gsat_attn_bwd_workspace_bytes": (SZ, [P]),
     "gsat_attn_fwd": (INT, [P, P]),
     "gsat_attn_bwd": (INT, [P, P, P]),
+    "gsat_attn_stream_plan": (INT, [P, I64, I64, P, P, P]),
+    "gsat_attn_stream_check": (INT, [P, P, P, P, P, I64, I64, I64, P, P]),
+    "gsat_attn_stream_fwd_workspace_bytes": (SZ, [P, I64]),
+    "gsat_attn_stream_fwd": (INT, [P, P, I64, P, P, I64, P]),
+    "gsat_attn_stream_bwd_workspace_bytes": (SZ, [P, P, I64, P, I64]),
+    "gsat_attn_stream_bwd": (INT, [P, P, P, I64, P, P, I64, P]),
     "gsat_instance_norm_fwd": (INT, [P, P, P, P, I64, I64, I64, P, P, P]),
     "gsat_instance_norm_bwd": (INT, [P, P, P, P, P, P, I64, I64, I64, P, P, P]),
     "gsat_philox_keep_mask": (INT, [U64, I32, I64, I64, F32, P, P]),

@@ -10,6 +10,8 @@
 //     the rest: segmented statistics, normalise + ReLU + Philox dropout, the head (C2 -> 1 dot + sampler, noise drawn
 //     in the kernel when no tensor is given), InstanceNorm backward, deterministic column sums.
 //   * all reductions run in a fixed order (no float atomics): results are bitwise reproducible.
+//   * attn_stream.h (included at the end): the memory-bounded edge-mode entry points, which run the layer-1 / layer-2 junction group of
+//     whole graphs by group through a scratch and share the whole-batch stages below (attn_fwd_tail, attn_bwd_head, attn_bwd_edge_nodes).
 #include "common.h"
 #include "attn_fused.h"
 #include <cstdlib>
@@ -751,6 +753,12 @@ static int check_args(const gsat_attn_args* a, const char* who) {
     return GSAT_OK;
 }
 
+// dW3 / db3 finished from the head kernel's partials in one launch (see attn_bwd_paths)
+static bool bwd_merged_ok(const gsat_attn_args* a, int Z) {
+    const char* env_m = getenv("GSAT_ATTN_BWD_MERGED");
+    const bool part_ok = (size_t)ceil_div(a->M, 256) <= (size_t)256 * std::max(a->C1, a->C2);
+    return Z == 1 && a->G > 0 && !(env_m && atoi(env_m) == 0) && part_ok;
+}
 // Every choice gsat_attn_bwd makes between kernels, from the arguments and the environment alone.  gsat_attn_bwd branches on these fields
 // and gsat_attn_paths reports them: one evaluation of the predicates, nothing restated.
 struct BwdPaths {
@@ -772,15 +780,111 @@ static BwdPaths attn_bwd_paths(const gsat_attn_args* a) {
     if (!p.fused) {
         // env GSAT_ATTN_BWD_MERGED=0: the round-2 sequence (two-stage column sums for db3 and dW3) also for unsliced segments (A/B switch).
         // The per-block sums of dz live in the column-sum scratch: 256 * max(C1, C2) >= M / 256 floats for M < 2^24 C
-        const char* env_m = getenv("GSAT_ATTN_BWD_MERGED");
-        const bool part_ok = (size_t)ceil_div(M, 256) <= (size_t)256 * std::max(C1, C2);
-        p.merged = Z == 1 && G > 0 && !(env_m && atoi(env_m) == 0) && part_ok;
+        p.merged = bwd_merged_ok(a, Z);
         p.dual2 = dual_gemm_ok(1, M, C2, C1, C1);
         p.pair2 = !p.dual2 && pair_ok(M, C2, C1, C1);
     }
     p.dual1 = dual_gemm_ok(2, N, C1, H, H);
     p.pair1 = !a->edge_mode && !p.dual1 && pair_ok(N, C1, H, H);
     return p;
+}
+
+// M == 0: every gradient is zero
+static int attn_bwd_zero(hipStream_t stream, const gsat_attn_args* a, const gsat_attn_grads* gr) {
+    const int64_t N = a->N;
+    const int H = a->H, C1 = a->C1, C2 = a->C2;
+    const int C0 = a->edge_mode ? 2 * H : H;
+    GSAT_CHECK_HIP(gsat::zero_async(gr->demb, sizeof(float) * N * H, stream));
+    GSAT_CHECK_HIP(gsat::zero_async(gr->dW1, sizeof(float) * C1 * C0, stream));
+    GSAT_CHECK_HIP(gsat::zero_async(gr->db1, sizeof(float) * C1, stream));
+    GSAT_CHECK_HIP(gsat::zero_async(gr->dW2, sizeof(float) * C2 * C1, stream));
+    GSAT_CHECK_HIP(gsat::zero_async(gr->db2, sizeof(float) * C2, stream));
+    GSAT_CHECK_HIP(gsat::zero_async(gr->dW3, sizeof(float) * C2, stream));
+    GSAT_CHECK_HIP(gsat::zero_async(gr->db3, sizeof(float), stream));
+    return GSAT_OK;
+}
+
+// From (dlogits, datt) through the head and the second InstanceNorm, over the whole batch: dz, db3, dW3, dh2 [M, C2]; db1 = db2 = 0.
+// The staged backward and the streamed one start with it.
+static int attn_bwd_head(hipStream_t stream, const gsat_attn_args* a, const gsat_attn_grads* gr, int Z, bool merged, float* dz, float* dh2, float* S1,
+                         float* S2, float* dw3p, float* scratch, float* zp1, float* zp2, float* zp3) {
+    const int64_t M = a->M, G = a->G;
+    const int C1 = a->C1, C2 = a->C2;
+    int rc;
+    float* mean2 = a->stats + (size_t)2 * G * C1;
+    float* rstd2 = mean2 + (size_t)G * C2;
+    const dim3 g2((unsigned)G, (unsigned)ceil_div(C2, 4 * SB_LANES), (unsigned)Z);
+    const unsigned dzb = (unsigned)ceil_div(M, 256);
+    float* dzpart = scratch;                         // [dzb] per-block sums of dz
+    // b1 and b2 sit in front of an InstanceNorm, which removes any per-channel constant of its segment: their
+    // gradients are exactly zero (the reference's autograd returns ~1e-7 rounding noise of a cancelling sum).
+    k_dz<<<dzb, 256, 0, stream>>>(gr->dlogits, gr->datt, a->att, M, dz, gr->db1, (int)C1, gr->db2, (int)C2, merged ? dzpart : nullptr);
+    GSAT_LAUNCH_CHECK();
+    if (!merged && (rc = colsum(stream, dz, M, 1, gr->db3, scratch))) return rc;
+    // ---- through the head and the second InstanceNorm ------------------------------------------
+    if (Z == 1)          // statistics and dh2 in one launch
+        k_head_bwd_stats<true><<<g2, SB, 0, stream>>>(a->h2, a->b2, a->seg_ptr, a->seg_order, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop,
+                                                      a->training, a->W3, DzSrc{dz, nullptr, nullptr, nullptr}, C2, S1, S2, dw3p, dh2);
+    else
+        k_head_bwd_stats<false><<<g2, SB, 0, stream>>>(a->h2, a->b2, a->seg_ptr, a->seg_order, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop,
+                                                       a->training, a->W3, DzSrc{dz, nullptr, nullptr, nullptr}, C2, zp1, zp2, zp3);
+    if (merged)     // dW3 and db3 from the partials, one launch (instead of two two-stage column sums)
+        k_head_bwd_finish<<<(unsigned)ceil_div(C2, 4 * SB_LANES) + 1, FIN_T, 0, stream>>>(dw3p, dzpart, G, (int)dzb, C2, gr->dW3, gr->db3);
+    if (Z > 1) {
+        const unsigned cb = (unsigned)ceil_div(G * C2, 256);
+        k_zcombine<<<cb, 256, 0, stream>>>(zp1, a->seg_ptr, (int)G, Z, C2, 1, S1);
+        k_zcombine<<<cb, 256, 0, stream>>>(zp2, a->seg_ptr, (int)G, Z, C2, 1, S2);
+        k_zcombine<<<cb, 256, 0, stream>>>(zp3, a->seg_ptr, (int)G, Z, C2, 0, dw3p);
+    }
+    GSAT_LAUNCH_CHECK();
+    if (!merged && (rc = colsum(stream, dw3p, G, C2, gr->dW3, scratch))) return rc;
+    if (Z > 1) {
+        k_dh2<<<ew_blocks(M * (C2 / 4)), 256, 0, stream>>>(a->h2, a->b2, a->row_seg, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop, a->training,
+                                                           a->W3, dz, S1, S2, M, C2, dh2);
+        GSAT_LAUNCH_CHECK();
+    }
+    return GSAT_OK;
+}
+
+// Edge mode, from dP / dQ [N, C1] to the node-level gradients: the end of the staged backward and of the streamed one
+static int attn_bwd_edge_nodes(hipStream_t stream, const gsat_attn_args* a, const gsat_attn_grads* gr, bool dual1, const float* dP, const float* dQ,
+                               char* dws, size_t dws_bytes, GemmWs gws1, GemmWs gws1b, SlabJob* jobs) {
+    const int64_t N = a->N;
+    const int H = a->H, C1 = a->C1;
+    int rc;
+    // demb = dP W1a + dQ W1b ; dW1[:, :H] = dP^T emb ; dW1[:, H:] = dQ^T emb
+    if (dual1) {
+        if ((rc = dual_gemm(stream, 2, N, C1, H, H, dP, C1, a->emb, H, a->W1, 2 * H, gr->demb, H, 0, gr->dW1, 2 * H, dws, dws_bytes))) return rc;
+        if ((rc = dual_gemm(stream, 2, N, C1, H, H, dQ, C1, a->emb, H, a->W1 + H, 2 * H, gr->demb, H, 1, gr->dW1 + H, 2 * H, dws, dws_bytes))) return rc;
+    } else {
+        if ((rc = gemm_rm(stream, false, false, N, H, C1, dP, C1, a->W1, 2 * H, 0.f, gr->demb, H, GemmWs{nullptr, 0}, true))) return rc;
+        if ((rc = gemm_rm(stream, false, false, N, H, C1, dQ, C1, a->W1 + H, 2 * H, 1.f, gr->demb, H, GemmWs{nullptr, 0}, true))) return rc;
+        if ((rc = gemm_rm(stream, true, false, C1, H, N, dP, C1, a->emb, H, 0.f, gr->dW1, 2 * H, gws1, true, &jobs[1]))) return rc;
+        if ((rc = gemm_rm(stream, true, false, C1, H, N, dQ, C1, a->emb, H, 0.f, gr->dW1 + H, 2 * H, gws1b, true, &jobs[2]))) return rc;
+    }
+    return GSAT_OK;
+}
+
+// layer-2 statistics over the whole batch, then the head and the sampler: the end of every forward that has h2 (staged and streamed)
+static int attn_fwd_tail(hipStream_t stream, const gsat_attn_args* a, int Z, float* part) {
+    const int64_t M = a->M, G = a->G;
+    const int C1 = a->C1, C2 = a->C2;
+    int rc;
+    float* mean2 = a->stats + (size_t)2 * G * C1;
+    float* rstd2 = mean2 + (size_t)G * C2;
+    {
+        PreAct<false> pre{a->h2, nullptr, a->b2, nullptr, nullptr, C2};
+        if ((rc = launch_seg_stats<false>(stream, pre, a->seg_ptr, a->seg_order, G, Z, mean2, rstd2, part))) return rc;
+    }
+    // ---- head + sampler ---------------------------------------------------------------------
+    const int q = C2 / 4;
+    const int lpr = q <= 4 ? 4 : q <= 8 ? 8 : q <= 16 ? 16 : q <= 32 ? 32 : 64;
+    const int nb = (int)std::min<int64_t>(ceil_div(M, 256 / lpr), 256 * 32);
+#define HEAD(L) k_head_fwd<L><<<nb, 256, 0, stream>>>(a->h2, a->b2, a->row_seg, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop, a->training, a->W3, a->b3, a->u, a->noise_philox, M, C2, a->logits, a->att)
+    switch (lpr) { case 4: HEAD(4); break; case 8: HEAD(8); break; case 16: HEAD(16); break; case 32: HEAD(32); break; default: HEAD(64); break; }
+#undef HEAD
+    GSAT_LAUNCH_CHECK();
+    return GSAT_OK;
 }
 
 }  // namespace gsat
@@ -813,8 +917,6 @@ int gsat_attn_fwd(const gsat_attn_args* a, void* stream_) {
     const int H = a->H, C1 = a->C1, C2 = a->C2;
     float* mean1 = a->stats;
     float* rstd1 = mean1 + (size_t)G * C1;
-    float* mean2 = rstd1 + (size_t)G * C1;
-    float* rstd2 = mean2 + (size_t)G * C2;
     // ---- layer 1 on nodes -------------------------------------------------------------------
     if (a->edge_mode) {
         if ((rc = gemm_rm(stream, false, true, N, C1, H, a->emb, H, a->W1, 2 * H, 0.f, a->P, C1))) return rc;        // P = emb W1[:, :H]^T
@@ -851,19 +953,7 @@ int gsat_attn_fwd(const gsat_attn_args* a, void* stream_) {
     GSAT_LAUNCH_CHECK();
     // ---- layer 2 ----------------------------------------------------------------------------
     if ((rc = gemm_rm(stream, false, true, M, C2, C1, a->a1, C1, a->W2, C1, 0.f, a->h2, C2))) return rc;
-    {
-        PreAct<false> pre{a->h2, nullptr, a->b2, nullptr, nullptr, C2};
-        if ((rc = launch_seg_stats<false>(stream, pre, a->seg_ptr, a->seg_order, G, Z, mean2, rstd2, part))) return rc;
-    }
-    // ---- head + sampler ---------------------------------------------------------------------
-    const int q = C2 / 4;
-    const int lpr = q <= 4 ? 4 : q <= 8 ? 8 : q <= 16 ? 16 : q <= 32 ? 32 : 64;
-    const int nb = (int)std::min<int64_t>(ceil_div(M, 256 / lpr), 256 * 32);
-#define HEAD(L) k_head_fwd<L><<<nb, 256, 0, stream>>>(a->h2, a->b2, a->row_seg, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop, a->training, a->W3, a->b3, a->u, a->noise_philox, M, C2, a->logits, a->att)
-    switch (lpr) { case 4: HEAD(4); break; case 8: HEAD(8); break; case 16: HEAD(16); break; case 32: HEAD(32); break; default: HEAD(64); break; }
-#undef HEAD
-    GSAT_LAUNCH_CHECK();
-    return GSAT_OK;
+    return attn_fwd_tail(stream, a, Z, part);
 }
 
 size_t gsat_attn_fwd_workspace_bytes(const gsat_attn_args* a) {
@@ -932,17 +1022,7 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
     GSAT_REQUIRE(gr && gr->demb && gr->dW1 && gr->db1 && gr->dW2 && gr->db2 && gr->dW3 && gr->db3, GSAT_ERR_ARG, "gsat_attn_bwd: null gradient output");
     const int64_t M = a->M, N = a->N, G = a->G;
     const int H = a->H, C1 = a->C1, C2 = a->C2;
-    const int C0 = a->edge_mode ? 2 * H : H;
-    if (M == 0) {
-        GSAT_CHECK_HIP(gsat::zero_async(gr->demb, sizeof(float) * N * H, stream));
-        GSAT_CHECK_HIP(gsat::zero_async(gr->dW1, sizeof(float) * C1 * C0, stream));
-        GSAT_CHECK_HIP(gsat::zero_async(gr->db1, sizeof(float) * C1, stream));
-        GSAT_CHECK_HIP(gsat::zero_async(gr->dW2, sizeof(float) * C2 * C1, stream));
-        GSAT_CHECK_HIP(gsat::zero_async(gr->db2, sizeof(float) * C2, stream));
-        GSAT_CHECK_HIP(gsat::zero_async(gr->dW3, sizeof(float) * C2, stream));
-        GSAT_CHECK_HIP(gsat::zero_async(gr->db3, sizeof(float), stream));
-        return GSAT_OK;
-    }
+    if (M == 0) return attn_bwd_zero(stream, a, gr);
     GSAT_REQUIRE(gr->dlogits || gr->datt, GSAT_ERR_ARG, "gsat_attn_bwd: need dlogits and/or datt");
     GSAT_REQUIRE(!gr->datt || a->att, GSAT_ERR_ARG, "gsat_attn_bwd: datt given but att was not saved");
     if (a->edge_mode) GSAT_REQUIRE(gr->rowptr_src && gr->eid_by_src && gr->rowptr_dst && gr->eid_by_dst, GSAT_ERR_ARG, "gsat_attn_bwd: edge mode needs both CSRs");
@@ -983,46 +1063,15 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
     GSAT_REQUIRE(ar.ok(), GSAT_ERR_WORKSPACE, "gsat_attn_bwd: workspace %zu < %zu", gr->workspace_bytes, ar.off);
     float* mean1 = a->stats;
     float* rstd1 = mean1 + (size_t)G * C1;
-    float* mean2 = rstd1 + (size_t)G * C1;
-    float* rstd2 = mean2 + (size_t)G * C2;
     const float sc = (a->training && a->p_drop > 0.f) ? 1.f / (1.f - a->p_drop) : 1.f;
 
     // b1 and b2 sit in front of an InstanceNorm, which removes any per-channel constant of its segment: their
     // gradients are exactly zero (the reference's autograd returns ~1e-7 rounding noise of a cancelling sum).
-    const dim3 g2((unsigned)G, (unsigned)ceil_div(C2, 4 * SB_LANES), (unsigned)Z), g1((unsigned)G, (unsigned)ceil_div(C1, 4 * SB_LANES), (unsigned)Z);
+    const dim3 g1((unsigned)G, (unsigned)ceil_div(C1, 4 * SB_LANES), (unsigned)Z);
     if (fused_bwd) {          // one launch from (dlogits, datt) down to dh1 (in the da1 buffer), dW2 / dW3 / db3 included (attn_fused_bwd.hip)
         if ((rc = attn_fused_bwd(stream, a, gr, da1, fws, fws_bytes))) return rc;
     } else {
-    const bool merged = bp.merged;
-    const unsigned dzb = (unsigned)ceil_div(M, 256);
-    float* dzpart = scratch;                         // [dzb] per-block sums of dz
-    // b1 and b2 sit in front of an InstanceNorm, which removes any per-channel constant of its segment: their
-    // gradients are exactly zero (the reference's autograd returns ~1e-7 rounding noise of a cancelling sum).
-    k_dz<<<dzb, 256, 0, stream>>>(gr->dlogits, gr->datt, a->att, M, dz, gr->db1, (int)C1, gr->db2, (int)C2, merged ? dzpart : nullptr);
-    GSAT_LAUNCH_CHECK();
-    if (!merged && (rc = colsum(stream, dz, M, 1, gr->db3, scratch))) return rc;
-    // ---- through the head and the second InstanceNorm ------------------------------------------
-    if (Z == 1)          // statistics and dh2 in one launch
-        k_head_bwd_stats<true><<<g2, SB, 0, stream>>>(a->h2, a->b2, a->seg_ptr, a->seg_order, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop,
-                                                      a->training, a->W3, DzSrc{dz, nullptr, nullptr, nullptr}, C2, S1, S2, dw3p, dh2);
-    else
-        k_head_bwd_stats<false><<<g2, SB, 0, stream>>>(a->h2, a->b2, a->seg_ptr, a->seg_order, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop,
-                                                       a->training, a->W3, DzSrc{dz, nullptr, nullptr, nullptr}, C2, zp1, zp2, zp3);
-    if (merged)     // dW3 and db3 from the partials, one launch (instead of two two-stage column sums)
-        k_head_bwd_finish<<<(unsigned)ceil_div(C2, 4 * SB_LANES) + 1, FIN_T, 0, stream>>>(dw3p, dzpart, G, (int)dzb, C2, gr->dW3, gr->db3);
-    if (Z > 1) {
-        const unsigned cb = (unsigned)ceil_div(G * C2, 256);
-        k_zcombine<<<cb, 256, 0, stream>>>(zp1, a->seg_ptr, (int)G, Z, C2, 1, S1);
-        k_zcombine<<<cb, 256, 0, stream>>>(zp2, a->seg_ptr, (int)G, Z, C2, 1, S2);
-        k_zcombine<<<cb, 256, 0, stream>>>(zp3, a->seg_ptr, (int)G, Z, C2, 0, dw3p);
-    }
-    GSAT_LAUNCH_CHECK();
-    if (!merged && (rc = colsum(stream, dw3p, G, C2, gr->dW3, scratch))) return rc;
-    if (Z > 1) {
-        k_dh2<<<ew_blocks(M * (C2 / 4)), 256, 0, stream>>>(a->h2, a->b2, a->row_seg, mean2, rstd2, a->mask2, SeedRef{a->seed, a->seed_dev}, a->p_drop, a->training,
-                                                           a->W3, dz, S1, S2, M, C2, dh2);
-        GSAT_LAUNCH_CHECK();
-    }
+    if ((rc = attn_bwd_head(stream, a, gr, Z, bp.merged, dz, dh2, S1, S2, dw3p, scratch, zp1, zp2, zp3))) return rc;
     // dW2[C2,C1] = dh2^T a1 ; da1[M,C1] = dh2 W2
     if (bp.dual2) {                                  // both products in one pass over dh2 (dual_gemm.hip)
         if ((rc = dual_gemm(stream, 1, M, C2, C1, C1, dh2, C2, a->a1, C1, a->W2, C1, da1, C1, 0, gr->dW2, C1, dws, dws_bytes))) return rc;
@@ -1062,16 +1111,7 @@ int gsat_attn_bwd(const gsat_attn_args* a, const gsat_attn_grads* gr, void* stre
                                     gr->chunk_ptr_src, lpart))) return rc;
         if ((rc = aggr_sum_fwd_impl(stream, da1, nullptr, nullptr, nullptr, gr->rowptr_dst, gr->eid_by_dst, nullptr, N, M, C1, 0.f, dQ,
                                     gr->chunk_ptr_dst, lpart))) return rc;
-        // demb = dP W1a + dQ W1b ; dW1[:, :H] = dP^T emb ; dW1[:, H:] = dQ^T emb
-        if (bp.dual1) {
-            if ((rc = dual_gemm(stream, 2, N, C1, H, H, dP, C1, a->emb, H, a->W1, 2 * H, gr->demb, H, 0, gr->dW1, 2 * H, dws, dws_bytes))) return rc;
-            if ((rc = dual_gemm(stream, 2, N, C1, H, H, dQ, C1, a->emb, H, a->W1 + H, 2 * H, gr->demb, H, 1, gr->dW1 + H, 2 * H, dws, dws_bytes))) return rc;
-        } else {
-        if ((rc = gemm_rm(stream, false, false, N, H, C1, dP, C1, a->W1, 2 * H, 0.f, gr->demb, H, GemmWs{nullptr, 0}, true))) return rc;
-        if ((rc = gemm_rm(stream, false, false, N, H, C1, dQ, C1, a->W1 + H, 2 * H, 1.f, gr->demb, H, GemmWs{nullptr, 0}, true))) return rc;
-        if ((rc = gemm_rm(stream, true, false, C1, H, N, dP, C1, a->emb, H, 0.f, gr->dW1, 2 * H, gws1, true, &jobs[1]))) return rc;
-        if ((rc = gemm_rm(stream, true, false, C1, H, N, dQ, C1, a->emb, H, 0.f, gr->dW1 + H, 2 * H, gws1b, true, &jobs[2]))) return rc;
-        }
+        if ((rc = attn_bwd_edge_nodes(stream, a, gr, bp.dual1, dP, dQ, dws, dws_bytes, gws1, gws1b, jobs))) return rc;
     } else {
         if (Z > 1) {
             PreAct<false> pre{a->P, nullptr, a->b1, nullptr, nullptr, C1};
@@ -1140,3 +1180,5 @@ int gsat_philox_keep_mask(uint64_t seed, int32_t layer, int64_t M, int64_t C, fl
 }
 
 }  // extern "C"
+
+#include "attn_stream.h"

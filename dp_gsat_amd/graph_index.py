@@ -377,6 +377,8 @@ class GraphSegments:
         self._flags = flags
         self._edge = None
         self._max_edges = None
+        self._stream_host = None          # (edge pointers, node pointers, verdict) on the host: stream_plan's one read
+        self._stream_plans = {}
 
     def check(self):
         self.index._checked = False
@@ -402,6 +404,40 @@ class GraphSegments:
             self._edge = (eptr, order, eg, eg32)
         return self._edge
 
+    def stream_plan(self, budget: int) -> "StreamPlan":
+        """The groups of whole graphs the memory-bounded extractor walks for a budget of ``budget`` edge rows (gsat_attn_stream_plan),
+        cached per budget.  The plan is a host decision, so the first call per collated batch makes ONE device->host read -- the edge
+        pointers, the node pointers and the verdict of gsat_attn_stream_check -- and raises ValueError for a batch that cannot be
+        streamed: edges not grouped by graph in edge order, or an edge between two graphs."""
+        import ctypes
+        budget = int(budget)
+        if budget < 1:
+            raise ValueError(f"stream_rows must be an int >= 1 (got {budget})")
+        if _SYNC_FREE or torch.cuda.is_current_stream_capturing():
+            raise ValueError("the streamed extractor plans its groups on the host per batch: not under stream capture or set_sync_free(True)")
+        if self._stream_host is None:
+            ix = self.index
+            eptr, _, _, eg32 = self.edge_segments
+            word = torch.empty(1, dtype=torch.int32, device=ix.device)
+            call("gsat_attn_stream_check", ptr(ix.src32), ptr(ix.dst32), ptr(self.node_seg32), ptr(eptr), ptr(eg32), ix.E, ix.N, self.G,
+                 ptr(word), stream())
+            host = torch.cat([eptr, self.node_ptr, word]).tolist()          # the one read of this batch
+            n = self.G + 1
+            self._stream_host = ((ctypes.c_int32 * n)(*host[:n]), (ctypes.c_int32 * n)(*host[n:2 * n]), int(host[2 * n]))
+        seg_h, node_h, verdict = self._stream_host
+        if verdict & 1:
+            raise ValueError("the streamed extractor needs the edges grouped by graph in edge order (a group's rows must be one range): "
+                             "this batch's edge order is not the identity")
+        if verdict & 2:
+            raise ValueError("the streamed extractor needs every edge inside one graph: this batch has an edge between two graphs")
+        plan = self._stream_plans.get(budget)
+        if plan is None:
+            group_ptr = (ctypes.c_int32 * (self.G + 1))()
+            n_groups, scratch_rows = ctypes.c_int64(), ctypes.c_int64()
+            call("gsat_attn_stream_plan", seg_h, self.G, budget, group_ptr, ctypes.byref(n_groups), ctypes.byref(scratch_rows))
+            plan = StreamPlan(group_ptr, n_groups.value, scratch_rows.value, seg_h, node_h)
+            self._stream_plans[budget] = plan
+        return plan
 
     @property
     def max_edges_per_graph(self) -> int:
@@ -413,6 +449,18 @@ class GraphSegments:
             eptr = self.edge_segments[0]
             self._max_edges = int((eptr[1:] - eptr[:-1]).max().item()) if self.G > 0 else 0
         return self._max_edges
+
+
+class StreamPlan:
+    """Host plan of the memory-bounded extractor: ``group_ptr`` [n_groups + 1] graph ids, ``scratch_rows`` = rows of the largest group,
+    and the host copies of the edge and node pointers the streamed entry points take (all ctypes int32 arrays)."""
+    __slots__ = ("group_ptr", "n_groups", "scratch_rows", "seg_ptr", "node_ptr")
+
+    def __init__(self, group_ptr, n_groups, scratch_rows, seg_ptr, node_ptr):
+        self.group_ptr, self.n_groups, self.scratch_rows, self.seg_ptr, self.node_ptr = group_ptr, int(n_groups), int(scratch_rows), seg_ptr, node_ptr
+
+    def groups(self):
+        return [int(self.group_ptr[i]) for i in range(self.n_groups + 1)]
 
 
 def call_size(name, *args) -> int:

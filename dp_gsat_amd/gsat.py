@@ -14,8 +14,8 @@ import torch.nn as nn
 from .get_model import MLP
 from .graph_index import get_index, sync_free
 from .padding import current_padding, padded
-from .ops import (ExtractorAttention, InfoLoss, Lift, LiftedAttention, Sample, SamplePhilox, Symmetrise, device_seed, edge_tensor,
-                  new_seed)
+from .ops import (ExtractorAttention, InfoLoss, Lift, LiftedAttention, Sample, SamplePhilox, StreamedExtractorAttention, Symmetrise,
+                  check_stream_request, device_seed, edge_tensor, new_seed)
 
 
 class ExtractorMLP(nn.Module):
@@ -25,10 +25,17 @@ class ExtractorMLP(nn.Module):
       ``ExtractorMLP(hidden_size, learn_edge_att)``            (example/gsat.py:122)
       ``ExtractorMLP(hidden_size, shared_config, type)``       (src/run_gsat.py:890; type in {"primal","dual"})
     and both call forms ``extractor(emb, edge_index, batch)`` / ``extractor(emb, edge_index, batch, type)``.
+
+    ``stream_rows`` (keyword or attribute, default None): an int >= 1 runs the edge-attention extractor memory-bounded -- the
+    [E, 4H] activation and its gradient exist only for a group of whole graphs of at most that many edge rows at a time (a larger graph
+    is a group of its own) and the backward computes the activation again; see ops.StreamedExtractorAttention.  Needs a batch whose
+    edges are grouped by graph (PyG collation) and is refused (ValueError) for node attention, under stream capture or
+    ``set_sync_free(True)`` and inside ``padded()``.  None changes nothing.
     """
 
-    def __init__(self, hidden_size, learn_edge_att_or_shared_config, type: Optional[str] = None):
+    def __init__(self, hidden_size, learn_edge_att_or_shared_config, type: Optional[str] = None, *, stream_rows: Optional[int] = None):
         super().__init__()
+        self.stream_rows = stream_rows
         cfg = learn_edge_att_or_shared_config
         if isinstance(cfg, dict):                                       # DP-GSAT form
             if type not in ("primal", "dual"):
@@ -59,6 +66,8 @@ class ExtractorMLP(nn.Module):
         ``noise``: uniform u in (0,1) per row -> concrete sample in training mode; None -> sigmoid(logits); the string
         "philox" -> concrete sample with u drawn inside the head kernel (Philox stream 4 of the step's seed, no noise tensor).
         ``dropout_masks``: optional explicit keep-masks [(M,C1),(M,C2)] (parity tests); default Philox(seed)."""
+        if self.stream_rows is not None:
+            check_stream_request(self.edge_mode, self.stream_rows)
         index = get_index(edge_index, emb.shape[0])
         segments = index.graphs(batch)
         l1, l2, l3 = self.mlp.linears()
@@ -76,6 +85,10 @@ class ExtractorMLP(nn.Module):
                 seed, seed_dev = 0, device_seed(emb.device)
             else:
                 seed = new_seed() if need else 0
+        if self.stream_rows is not None:
+            return StreamedExtractorAttention.apply(emb, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, index, segments,
+                                                    self.edge_mode, self.training, self.mlp.dropout_p, seed, m1, m2, noise, seed_dev, philox_noise,
+                                                    self.stream_rows)
         return ExtractorAttention.apply(emb, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, index, segments,
                                         self.edge_mode, self.training, self.mlp.dropout_p, seed, m1, m2, noise, seed_dev, philox_noise)
 

@@ -491,6 +491,102 @@ class ExtractorAttention(torch.autograd.Function):
         return (demb, *grads, None, None, None, None, None, None, None, None, None, None, None)
 
 
+def check_stream_request(edge_mode, stream_rows):
+    """The refusals of the streamed extractor that need no look at the batch: ValueError before anything is launched."""
+    from .graph_index import sync_free
+    from .padding import current_padding
+    if not edge_mode:
+        raise ValueError("stream_rows needs an edge-attention extractor (node attention keeps no [E, 4H] tensor)")
+    if isinstance(stream_rows, bool) or not isinstance(stream_rows, int) or stream_rows < 1:
+        raise ValueError(f"stream_rows must be an int >= 1 (got {stream_rows!r})")
+    if sync_free() or torch.cuda.is_current_stream_capturing():
+        raise ValueError("the streamed extractor plans its groups on the host per batch: not under stream capture or set_sync_free(True)")
+    if current_padding() is not None:
+        raise ValueError("the streamed extractor does not run inside padded(): padded batches belong to the replayed steps")
+
+
+class StreamedExtractorAttention(torch.autograd.Function):
+    """ExtractorAttention for edge-attention batches whose [E, 4H] activations do not fit, or should not be spent: the junction of layer 1
+    and layer 2 runs group of whole graphs by group through a scratch of ``plan.scratch_rows`` rows (gsat_attn_stream_fwd / _bwd).  Saved
+    for the backward: P, Q, h2, the statistics, att -- no [M, C1] tensor; the backward computes a group's a1 again.  Same arguments as
+    ExtractorAttention plus the trailing ``stream_rows`` (row budget of a group, an int >= 1).  The same seed, masks and noise give the
+    keep decisions and the sample of the unstreamed step: every draw is keyed by the global row."""
+
+    @staticmethod
+    def forward(ctx, emb, W1, b1, W2, b2, W3, b3, index, segments, edge_mode, training, p, seed, mask1, mask2, u, seed_dev=None, noise_philox=False,
+                stream_rows=None):
+        import ctypes
+        check_stream_request(edge_mode, stream_rows)
+        plan = segments.stream_plan(stream_rows)          # ValueError: capture / sync-free mode, rows not grouped by graph, cross-graph edge
+        ctx.set_materialize_grads(False)
+        emb = _f32c(emb)
+        params = tuple(_f32c(t) for t in (W1, b1, W2, b2, W3, b3))
+        mask1, mask2 = _f32c(mask1), _f32c(mask2)
+        u = None if u is None else _f32c(u).view(-1)
+        N, H = emb.shape
+        C1, C2 = params[0].shape[0], params[2].shape[0]
+        if params[0].shape[1] != 2 * H or params[2].shape[1] != C1 or tuple(params[4].shape) != (1, C2):
+            raise ValueError("extractor weight shapes do not match the embedding width")
+        if N != index.N:
+            raise ValueError(f"emb has {N} rows but the index was built for {index.N} nodes")
+        M = index.E
+        for m_, c_ in ((mask1, C1), (mask2, C2)):
+            if m_ is not None and tuple(m_.shape) != (M, c_):
+                raise ValueError("dropout keep-mask has the wrong shape")
+        if u is not None and u.numel() != M:
+            raise ValueError("noise tensor has the wrong number of entries")
+        dev, f32 = emb.device, torch.float32
+        G = segments.G
+        P = torch.empty(N, C1, dtype=f32, device=dev)
+        Q = torch.empty(N, C1, dtype=f32, device=dev)
+        h2 = torch.empty(M, C2, dtype=f32, device=dev)
+        stats = torch.empty(max(G, 1) * (2 * C1 + 2 * C2), dtype=f32, device=dev)
+        logits = torch.empty(M, 1, dtype=f32, device=dev)
+        att = torch.empty(M, 1, dtype=f32, device=dev)
+        args = _attn_args(emb, params, index, segments, True, training, p, seed, mask1, mask2, u, (P, Q, None, h2, stats, logits, att), seed_dev,
+                          noise_philox)
+        args.seg_order = None                                # the plan has verified that the edge order is the identity
+        from ._lib import load
+        fws_bytes = int(load().gsat_attn_stream_fwd_workspace_bytes(ctypes.byref(args), plan.scratch_rows))
+        fws = torch.empty(fws_bytes, dtype=torch.uint8, device=dev)
+        args.fwd_workspace, args.fwd_workspace_bytes = ptr(fws), fws_bytes
+        call("gsat_attn_stream_fwd", ctypes.byref(args), plan.group_ptr, plan.n_groups, plan.seg_ptr, plan.node_ptr, plan.scratch_rows, stream())
+        ctx.save_for_backward(emb, *params, P, Q, h2, stats, att,
+                              mask1 if mask1 is not None else emb.new_empty(0),
+                              mask2 if mask2 is not None else emb.new_empty(0))
+        ctx.meta = (index, segments, plan, bool(training), float(p), int(seed), mask1 is not None, mask2 is not None)
+        ctx.seed_dev = seed_dev
+        return logits, att
+
+    @staticmethod
+    def backward(ctx, dlogits, datt):
+        import ctypes
+        from ._lib import AttnGrads, load
+        (emb, W1, b1, W2, b2, W3, b3, P, Q, h2, stats, att, mask1, mask2) = ctx.saved_tensors
+        index, segments, plan, training, p, seed, has_m1, has_m2 = ctx.meta
+        params = (W1, b1, W2, b2, W3, b3)
+        args = _attn_args(emb, params, index, segments, True, training, p, seed, mask1 if has_m1 else None, mask2 if has_m2 else None, None,
+                          (P, Q, None, h2, stats, att, att), ctx.seed_dev)          # the logits slot is not read by the backward
+        args.seg_order = None
+        g = AttnGrads()
+        dlogits = None if dlogits is None else _f32c(dlogits)
+        datt = None if datt is None else _f32c(datt)
+        g.dlogits, g.datt = ptr(dlogits), ptr(datt)
+        g.rowptr_src, g.eid_by_src = ptr(index.rowptr_src), ptr(index.eid_by_src)
+        g.rowptr_dst, g.eid_by_dst = ptr(index.rowptr_dst), ptr(index.eid_by_dst)
+        g.chunk_ptr_dst, g.chunk_ptr_src = (ptr(t) for t in index.long_rows)
+        demb = torch.empty_like(emb)
+        grads = [torch.empty_like(t) for t in params]
+        g.demb = ptr(demb)
+        g.dW1, g.db1, g.dW2, g.db2, g.dW3, g.db3 = (ptr(t) for t in grads)
+        ws_bytes = int(load().gsat_attn_stream_bwd_workspace_bytes(ctypes.byref(args), plan.group_ptr, plan.n_groups, plan.seg_ptr, plan.scratch_rows))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=emb.device)
+        g.workspace, g.workspace_bytes = ptr(ws), ws_bytes
+        call("gsat_attn_stream_bwd", ctypes.byref(args), ctypes.byref(g), plan.group_ptr, plan.n_groups, plan.seg_ptr, plan.node_ptr,
+             plan.scratch_rows, stream())
+        return (demb, *grads) + (None,) * 12
+
+
 def new_seed() -> int:
     """63-bit Philox seed drawn from torch's CPU generator (follows torch.manual_seed, no device sync)."""
     return int(torch.empty((), dtype=torch.int64).random_().item())

@@ -567,6 +567,42 @@ size_t gsat_attn_bwd_workspace_bytes(const gsat_attn_args* args);
 int gsat_attn_fwd(const gsat_attn_args* args, void* stream);
 int gsat_attn_bwd(const gsat_attn_args* args, const gsat_attn_grads* grads, void* stream);
 
+/* ---- memory-bounded edge-mode extractor: a1 and da1 streamed by groups of whole graphs ------------------------------------------------
+ * gsat_attn_fwd saves a1 [M, C1] and gsat_attn_bwd takes a second [M, C1] buffer (da1 -> dh1) from its workspace: with M = E and
+ * C1 = 4H these two are most of the memory of a step on large graphs.  The per-graph InstanceNorm makes graphs independent everywhere
+ * but in the weight-gradient sums, so the entry points below run the junction of layer 1 and layer 2 one GROUP of consecutive graphs at
+ * a time through a scratch of `scratch_rows` rows.  Saved between forward and backward: P, Q, h2, stats, att -- no [M, C1] tensor; the
+ * backward computes a group's a1 again from P, Q, b1, the saved statistics and the keep decisions (Philox draws and explicit masks are
+ * keyed by the GLOBAL row, so a streamed step uses the keep decisions and the noise of the unstreamed one).  Edge mode only
+ * (GSAT_ERR_UNSUPPORTED otherwise); no float atomics, groups run in order: two runs with one plan are bitwise equal.
+ *
+ * gsat_attn_stream_plan: HOST code, no launch.  seg_ptr [G+1] (HOST: edge rows per graph), budget >= 1 rows.  Greedy in graph order: a
+ *   group is the longest run of consecutive graphs whose rows sum to <= budget; a graph with more rows is a group of its own; graphs
+ *   without rows never open a group (they join the group before them, or the first one).  Writes group_ptr [n_groups+1] (graph ids;
+ *   room for G+1 entries), n_groups and scratch_rows = the largest row count of a group, at least 1.
+ * gsat_attn_stream_check: ONE launch; stores into the DEVICE word `verdict` the OR of GSAT_ATTN_STREAM_BAD_ORDER (some row m lies
+ *   outside [seg_ptr[row_seg[m]], seg_ptr[row_seg[m]+1]): rows are not grouped by graph in row order) and GSAT_ATTN_STREAM_BAD_CROSS
+ *   (node_seg[src[m]] != node_seg[dst[m]], or != row_seg[m]: an edge joins two graphs); 0 = the batch can be streamed.  Streaming rests
+ *   on both: a group's rows are one contiguous range, and the CSR rows of a group's nodes hold edge ids of that range only.
+ * gsat_attn_stream_fwd / _bwd: `args` / `grads` as for gsat_attn_fwd / gsat_attn_bwd with args->a1 == NULL (not read) and
+ *   args->seg_order == NULL (required); args->fwd_workspace holds gsat_attn_stream_fwd_workspace_bytes() bytes and grads->workspace
+ *   gsat_attn_stream_bwd_workspace_bytes() bytes.  group_ptr / n_groups / scratch_rows: a plan as gsat_attn_stream_plan writes it (any
+ *   partition of [0, G) into runs of at most scratch_rows rows is accepted); seg_ptr_host / node_ptr_host: HOST copies of args->seg_ptr
+ *   and args->node_ptr.  The plan is validated on the host before the first launch.  db1 = db2 = 0 exactly, as in gsat_attn_bwd.
+ */
+#define GSAT_ATTN_STREAM_BAD_ORDER 1
+#define GSAT_ATTN_STREAM_BAD_CROSS 2
+int gsat_attn_stream_plan(const int32_t* seg_ptr, int64_t G, int64_t budget, int32_t* group_ptr, int64_t* n_groups, int64_t* scratch_rows);
+int gsat_attn_stream_check(const int32_t* src, const int32_t* dst, const int32_t* node_seg, const int32_t* seg_ptr, const int32_t* row_seg,
+                           int64_t M, int64_t N, int64_t G, int32_t* verdict, void* stream);
+size_t gsat_attn_stream_fwd_workspace_bytes(const gsat_attn_args* args, int64_t scratch_rows);
+int gsat_attn_stream_fwd(const gsat_attn_args* args, const int32_t* group_ptr, int64_t n_groups, const int32_t* seg_ptr_host,
+                         const int32_t* node_ptr_host, int64_t scratch_rows, void* stream);
+size_t gsat_attn_stream_bwd_workspace_bytes(const gsat_attn_args* args, const int32_t* group_ptr, int64_t n_groups,
+                                            const int32_t* seg_ptr_host, int64_t scratch_rows);
+int gsat_attn_stream_bwd(const gsat_attn_args* args, const gsat_attn_grads* grads, const int32_t* group_ptr, int64_t n_groups,
+                         const int32_t* seg_ptr_host, const int32_t* node_ptr_host, int64_t scratch_rows, void* stream);
+
 /* Standalone per-graph InstanceNorm (src/utils/get_model.py:50-51,64) for BatchSequential users.
  * y = (x - mean_g) * rstd_g ; stats [G*2*C] = mean | rstd (saved for backward). */
 int gsat_instance_norm_fwd(const float* x, const int32_t* seg_ptr, const int32_t* seg_order,
