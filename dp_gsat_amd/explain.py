@@ -290,8 +290,10 @@ def _node_segments(batch, num_graphs):
         raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
     if batch.dtype != torch.int64 or batch.dim() != 1:
         raise ValueError("batch must be an int64 vector")
-    key = (batch.data_ptr(), batch._version, int(batch.shape[0]))
-    for ix in _CACHE.values():
+    from .graph_index import tensor_version
+    version = tensor_version(batch)
+    key = (batch.data_ptr(), version, int(batch.shape[0]))
+    for ix in (_CACHE.values() if version is not None else ()):
         seg = ix._graphs.get(key)
         if seg is not None and (num_graphs is None or seg.G == int(num_graphs)):
             return seg.node_ptr, seg.node_seg32, seg.G

@@ -23,8 +23,10 @@ class _SegmentCache:
         self.key, self.val = None, None
 
     def get(self, batch: torch.Tensor, num_seg=None):
-        key = (batch.data_ptr(), batch._version, int(batch.shape[0]), num_seg)
-        if key == self.key:
+        from .graph_index import tensor_version
+        version = tensor_version(batch)
+        key = (batch.data_ptr(), version, int(batch.shape[0]), num_seg) if version is not None else None
+        if key is not None and key == self.key:
             return self.val
         if batch.dtype != torch.int64 or batch.dim() != 1:
             raise ValueError("batch must be an int64 vector")

@@ -97,6 +97,12 @@ def sync_free() -> bool:
     return _SYNC_FREE
 
 
+def tensor_version(t: torch.Tensor) -> Optional[int]:
+    """``t._version`` for a cache key, or None for an inference tensor (made under ``torch.inference_mode()``), which tracks none: a cache
+    keyed on such a tensor could not see an in-place edit, so the callers build afresh instead of looking it up."""
+    return None if t.is_inference() else t._version
+
+
 def _i32(n, device):
     return torch.empty(max(int(n), 1), dtype=torch.int32, device=device)[: int(n)]
 
@@ -232,11 +238,13 @@ class BatchIndex:
         (the warm-up runs that precede a capture), and never again for the same tensors."""
         # keyed on the tensors' storage AND their versions: a new batch that lands on a recycled allocation of the same shape (or an
         # in-place edit) is validated again
-        key = (self.edge_index.data_ptr(), self._key_tensor._version, tuple(self.edge_index.shape), self.N,
-               tuple(k for k in self._graphs))
+        version = tensor_version(self._key_tensor)
+        key = (self.edge_index.data_ptr(), version, tuple(self.edge_index.shape), self.N, tuple(k for k in self._graphs))
         if key in _VALIDATED or torch.cuda.is_current_stream_capturing():
             return
         self._readback()
+        if version is None or any(k[1] is None for k in self._graphs):
+            return
         if len(_VALIDATED) > 4096:
             _VALIDATED.clear()
         _VALIDATED.add(key)
@@ -343,8 +351,9 @@ class BatchIndex:
 
     # -- per-graph segments ----------------------------------------------------------------------
     def graphs(self, batch: torch.Tensor, num_graphs: Optional[int] = None) -> "GraphSegments":
-        key = (batch.data_ptr(), batch._version, int(batch.shape[0]))
-        seg = self._graphs.get(key)
+        version = tensor_version(batch)
+        key = (batch.data_ptr(), version, int(batch.shape[0]))
+        seg = self._graphs.get(key) if version is not None else None
         if seg is None:
             if not self._err3_fresh:
                 self._err[3:4].zero_()             # the order / range counter belongs to the batch vector being registered
@@ -477,7 +486,10 @@ _CACHE_SIZE = 8
 
 
 def get_index(edge_index: torch.Tensor, num_nodes: int) -> BatchIndex:
-    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), int(num_nodes), str(edge_index.device))
+    version = tensor_version(edge_index)
+    if version is None:
+        return BatchIndex(edge_index, num_nodes)
+    key = (edge_index.data_ptr(), version, tuple(edge_index.shape), int(num_nodes), str(edge_index.device))
     ix = _CACHE.get(key)
     if ix is None:
         ix = BatchIndex(edge_index, num_nodes)

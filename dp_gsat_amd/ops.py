@@ -36,6 +36,12 @@ def _flat_att(att: Optional[torch.Tensor], E: int) -> Optional[torch.Tensor]:
     return _f32c(att).view(-1)
 
 
+def _backward_pass_id() -> int:
+    """autograd's id of the backward pass (graph task) that is running on this thread; -1 outside a pass or where this torch cannot tell."""
+    current = getattr(torch._C, "_current_graph_task_id", None)
+    return -1 if current is None else int(current())
+
+
 class LiftedAttention:
     """``node_att[src] * node_att[dst]`` (example/gsat.py:112-117) that has not been written out: the PNA aggregation forms the product
     at its mask load (gsat_pna_*_node_att), so a node-attention step needs no [E] tensor and no lift kernels.  Every other consumer --
@@ -49,7 +55,7 @@ class LiftedAttention:
         # output of one autograd node (_SharedAttention) that only they consume; the first of their backward nodes to run writes the
         # buffer and hands it to autograd, the others add to it inside their own kernel and return nothing (no [N,1] add launch per
         # layer); _SharedAttention.backward runs after all of them, passes the sum on to node_att (where autograd may add other consumers'
-        # gradients, e.g. the info loss) and clears the state for a second backward through a retained graph.
+        # gradients, e.g. the info loss) and drops the buffer.  _dna = (id of the backward pass, buffer): see _shared_dna.
         self._dna = None
         self._shared = None
 
@@ -60,12 +66,20 @@ class LiftedAttention:
         return self._shared
 
     def _shared_dna(self, N, device):
-        """(buffer, accumulate, what to return to autograd) for one layer's d node_att."""
-        if self._dna is None or os.environ.get("GSAT_NODE_ATT_SHARED_GRAD", "1") == "0":
+        """(buffer, accumulate, what to return to autograd) for one layer's d node_att.  The shared buffer belongs to ONE backward pass
+        (autograd's graph task id), not to this object: a pass that never reaches _SharedAttention.backward -- torch.autograd.grad on
+        other inputs prunes that node, an exception cuts the pass short -- leaves a buffer that the next pass does not add into.  Where
+        the pass cannot be identified every layer gets a buffer of its own and autograd adds them (GSAT_NODE_ATT_SHARED_GRAD=0)."""
+        task = _backward_pass_id()
+        if task < 0 or os.environ.get("GSAT_NODE_ATT_SHARED_GRAD", "1") == "0":
+            self._dna = None
             buf = torch.empty(N, dtype=torch.float32, device=device)
-            self._dna = buf if os.environ.get("GSAT_NODE_ATT_SHARED_GRAD", "1") != "0" else None
             return buf, 0, buf
-        return self._dna, 1, None
+        if self._dna is None or self._dna[0] != task:
+            buf = torch.empty(N, dtype=torch.float32, device=device)
+            self._dna = (task, buf)
+            return buf, 0, buf
+        return self._dna[1], 1, None
 
     def edge(self) -> torch.Tensor:
         if self._edge is None:
@@ -101,6 +115,7 @@ class _SharedAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, node_att, owner):
         ctx.owner = owner
+        ctx.set_materialize_grads(False)          # no layer sent a gradient (only their pass-through outputs were used): None, not zeros
         return node_att.view_as(node_att)
 
     @staticmethod
@@ -867,7 +882,8 @@ class EmbeddingSum(torch.autograd.Function):
         d_arr = (ctypes.c_int32 * len(dims))(*dims)
         out = torch.empty(N, H, dtype=torch.float32, device=W.device)
         call("gsat_embsum_fwd", ptr(x_idx), d_arr, len(dims), ptr(W), N, H, ptr(out), stream())
-        ctx.x_idx, ctx.dims, ctx.cache, ctx.R = x_idx, tuple(dims), onehot_cache, W.shape[0]
+        ctx.save_for_backward(x_idx)              # under autograd's version check: an in-place edit before the backward raises
+        ctx.dims, ctx.cache, ctx.R = tuple(dims), onehot_cache, W.shape[0]
         return out
 
     @staticmethod
@@ -875,7 +891,8 @@ class EmbeddingSum(torch.autograd.Function):
         import ctypes
         from ._lib import load
         dout = _f32c(dout)
-        x_idx, dims, R = ctx.x_idx, ctx.dims, ctx.R
+        (x_idx,) = ctx.saved_tensors
+        dims, R = ctx.dims, ctx.R
         N, H = dout.shape
         Rp = (R + 3) // 4 * 4
         key = (x_idx.data_ptr(), x_idx._version, N)
@@ -1026,6 +1043,8 @@ class ReluDropout(torch.autograd.Function):
 def relu_dropout(x, p: float, training: bool):
     """F.dropout(relu(x), p, training) -- HIP for 2-D fp32 ROCm tensors with a width that is a multiple of 4, torch otherwise."""
     p = float(p) if training else 0.0
+    if p >= 1.0:
+        return x * 0.0           # F.dropout(relu(x), 1.0): zeros with a zero gradient; the kernel's 1/(1-p) has no such case
     if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[1] % 4 == 0):
         return torch.nn.functional.dropout(torch.relu(x), p, training=True) if p > 0.0 else torch.relu(x)
     seed, seed_dev = 0, None
