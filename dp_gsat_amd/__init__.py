@@ -31,6 +31,9 @@ from .subgraph import explanation_node_fidelity_curve, explanation_node_subgraph
 from .evaluate import (AttentionHistogram, EvaluationMeter, attention_histogram, classifier_accuracy, classifier_rocauc, classifier_rocauc_tasks, pr_curve,
                        task_auroc_counts)
 from .eval_log import EpochLog, FidelityCurveLog, FidelityLog, delta_kl_segments
+from .eval_log import ClfLog
+from .replay import ReplayedClfEval, ReplayedClfStep
+from .pretrain import pretrain_clf, update_best_clf
 
 __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "get_preds", "GINConv", "GINEConv",
            "PNAConvSimple", "GIN", "PNA", "GSAT", "ExtractorMLP", "concrete_sample", "get_r", "gumbel_sigmoid",
@@ -45,4 +48,5 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "explanation_levels", "StackedExplanationBatch", "explanation_stack", "explanation_fidelity_curve", "FidelityCurveLog",
            "ReplayedFidelityCurve", "explanation_stack_multi", "explanation_fidelity_curves", "level_overlap",
            "ReplayedDualFidelityCurve", "NodeRanking", "rank_nodes", "topk_node_mask", "node_levels", "node_precision_at_k",
-           "explanation_node_subgraph", "explanation_stack_nodes", "explanation_node_fidelity_curve"]
+           "explanation_node_subgraph", "explanation_stack_nodes", "explanation_node_fidelity_curve",
+           "ClfLog", "ReplayedClfStep", "ReplayedClfEval", "pretrain_clf", "update_best_clf"]

@@ -143,6 +143,9 @@ SIGNATURES = {
     "gsat_delta_kl_segments_chunk": (I64, []),
     "gsat_delta_kl_segments_workspace_bytes": (SZ, [I64, I64]),
     "gsat_delta_kl_segments": (INT, [P, P, P, I64, I64, I64, F64, P, P, SZ, P]),
+    "gsat_clf_log_append": (INT, [P] * 4 + [I64] * 3 + [P] * 4 + [I64] * 2 + [P]),
+    "gsat_clf_log_counts_words": (I64, [I64, I64, INT]),
+    "gsat_clf_log_counts": (INT, [P, P, P, I64, I64, I64, INT, P, P]),
     "gsat_fidelity_append": (INT, [P, P, P, I64, I64, P, P, P, P, I64, P]),
     "gsat_fidelity_reduce": (INT, [P, P, P, I64, P, P]),
     "gsat_fidelity_reset": (INT, [P, P]),

@@ -414,3 +414,122 @@ class FidelityCurveLog:
             res[key + "_tasks"] = [[float(a[t, s]) for t in range(T)] for s in range(S)]
             res[key] = [float(np.mean(np.array(row, dtype=np.float64))) for row in res[key + "_tasks"]]
         return res
+
+
+def _clf_mode(multi_label: bool, logit_cols: int) -> int:
+    """The mode of ``criterion_valid``: 0 binary (one logit), 1 multi-class, 2 multi-label."""
+    return 2 if multi_label else (0 if logit_cols == 1 else 1)
+
+
+class ClfLog:
+    """``ClfLog(max_graphs, max_batches, logit_cols, y_cols=1, multi_label=False, device=None)``: the device log of a classifier epoch
+    (csrc/clf_log.hip) -- what the ERM loop of src/pretrain_clf.py keeps per batch -- allocated once (plain attributes: their addresses
+    never change): ``logits`` fp32[max_graphs, logit_cols], ``y`` fp32[max_graphs, y_cols] (NaN = unlabelled), ``loss_sum`` float64[1] and
+    ``state`` int64[4] = (graphs, batches, flags, 0) on the device.  ``append`` is two kernel launches and reads nothing, so it replays
+    inside a captured graph (``ReplayedClfStep``, ``ReplayedClfEval``); ``compute`` reads the device twice.  An append that cannot be
+    taken -- a padded batch whose overflow word is set (flag bit 0), or one whose count is outside its own rows or that would exceed
+    ``max_graphs`` or ``max_batches`` (flag bit 1) -- writes nothing but its flag and is reported by ``compute``.
+
+    The predicted class is ``z > 0`` for one logit column and for a multi-label head, and the argmax (lowest index on ties) for several
+    classes.  ``z > 0`` differs from ``get_preds``'s ``sigmoid(z) > 0.5`` only where the fp32 sigmoid of a non-zero ``z`` rounds to exactly
+    0.5, which is ``|z|`` below about 1e-7."""
+
+    def __init__(self, max_graphs: int, max_batches: int, logit_cols: int, y_cols: int = 1, multi_label: bool = False, device=None):
+        if min(int(max_graphs), int(max_batches)) < 0 or int(logit_cols) < 1 or int(y_cols) < 1:
+            raise ValueError("ClfLog needs non-negative capacities and at least one logit and one label column")
+        if int(max_graphs) >= 2 ** 31:
+            raise ValueError("ClfLog: max_graphs must be below 2**31")
+        self.max_graphs, self.max_batches = int(max_graphs), int(max_batches)
+        self.logit_cols, self.y_cols, self.multi_label = int(logit_cols), int(y_cols), bool(multi_label)
+        self.mode = _clf_mode(self.multi_label, self.logit_cols)
+        if self.mode == 2 and self.y_cols != self.logit_cols:
+            raise ValueError("ClfLog: a multi-label head has one label column per logit column")
+        if self.mode != 2 and self.y_cols != 1:
+            raise ValueError("ClfLog: a single-label head has one label column")
+        if (self.mode == 1 and self.logit_cols > 32) or (self.mode == 2 and self.logit_cols > 256):
+            raise ValueError("ClfLog: the counting kernel takes at most 32 classes or 256 tasks")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise GsatHipError("dp_gsat_amd.eval_log needs a ROCm (cuda) device: the HIP path has no CPU fallback")
+        self.logits = torch.empty((self.max_graphs, self.logit_cols), dtype=torch.float32, device=dev)
+        self.y = torch.empty((self.max_graphs, self.y_cols), dtype=torch.float32, device=dev)
+        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.state = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._words = call_size("gsat_clf_log_counts_words", self.logit_cols, self.y_cols, self.mode)
+        self._out = torch.empty(self._words, dtype=torch.int64, device=dev)
+
+    def reset(self) -> None:
+        """Empty the log: ``state`` and ``loss_sum`` are zeroed on the device, nothing is read."""
+        self.state.zero_()
+        self.loss_sum.zero_()
+
+    def append(self, data, clf_logits, loss=None) -> None:
+        """Log one batch.  ``data``: a collated batch with ``y`` and ``num_graphs``; for a ``PaddedBatch`` the real graphs are counted by
+        ``data.valid`` on the device and ``clf_logits`` has capacity shape ``[num_graphs, logit_cols]``.  ``loss``: one float on the
+        device, or None (the epoch's mean loss is then NaN).  Kernels only: nothing is read back."""
+        if not isinstance(clf_logits, torch.Tensor) or not clf_logits.is_cuda or not data.y.is_cuda:
+            raise GsatHipError("dp_gsat_amd.eval_log needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+        G_cap = int(data.num_graphs)
+        if clf_logits.dim() != 2 or tuple(clf_logits.shape) != (G_cap, self.logit_cols):
+            raise ValueError(f"clf_logits must have shape [{G_cap}, {self.logit_cols}], one row per graph of the batch")
+        if data.y.shape[0] != G_cap or data.y.numel() != G_cap * self.y_cols:
+            raise ValueError(f"data.y must have {G_cap} rows of {self.y_cols} labels")
+        logits = clf_logits.detach().to(torch.float32).contiguous()
+        y = data.y.detach().reshape(G_cap, self.y_cols).to(torch.float32).contiguous()
+        valid = getattr(data, "valid", None)
+        if valid is not None and (valid.dtype != torch.int32 or valid.numel() < 4 or not valid.is_cuda):
+            raise ValueError("data.valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+        if loss is not None:
+            if not isinstance(loss, torch.Tensor) or not loss.is_cuda or loss.numel() != 1:
+                raise ValueError("loss must be a ROCm tensor of one entry")
+            loss = loss.detach().reshape(1).to(torch.float32).contiguous()
+        some = lambda t: ptr(t) if t.numel() else None
+        call("gsat_clf_log_append", some(logits), some(y), ptr(valid.contiguous()) if valid is not None else None,
+             ptr(loss) if loss is not None else None, G_cap, self.logit_cols, self.y_cols, some(self.logits), some(self.y),
+             ptr(self.loss_sum), ptr(self.state), self.max_graphs, self.max_batches, stream())
+
+    def compute(self) -> dict:
+        """Score everything logged since ``reset``.  ``n``; ``clf_acc`` -- single label: trace of the confusion matrix / n; multi-label:
+        ``(tn + tp)`` over all tasks / ``(n * T)``, an unlabelled entry never matching (src/pretrain_clf.py:97); ``clf_roc`` --
+        ``classifier_rocauc`` on the logged rows, 0.0 for multi-class as in ``EpochLog``; ``loss`` = ``loss_sum`` / batches (NaN when a
+        batch came without a loss).  Single label: ``confusion`` numpy int64[C, C] (rows the label, columns the prediction; C = 2 for one
+        logit) and ``bad``, the rows with a label that is no class or a NaN logit (they match nothing).  Multi-label: ``task_counts``
+        int64[T, 4] = (tn, fp, fn, tp) per task, ``unlabelled`` int64[T] and ``clf_roc_tasks`` float64[T] (NaN for a task without both
+        classes).  Exactly two host reads: the counts in ``state``, then the packed results.  ValueError when an append was refused,
+        or nothing was appended."""
+        n, nb, flags, _ = self.state.tolist()                                                   # the first host read
+        if flags & FLAG_OVERFLOW:
+            raise ValueError("ClfLog: flag bit 0 is set -- a padded batch did not fit its capacity (valid[3]) and was not logged")
+        if flags & FLAG_FULL:
+            raise ValueError("ClfLog: flag bit 1 is set -- an append had a count outside its own rows or would have exceeded max_graphs "
+                             f"or max_batches ({self.max_graphs}, {self.max_batches}) and was not logged")
+        if nb == 0:
+            raise ValueError("ClfLog.compute() before any append()")
+        dev = self.state.device
+        some = lambda t: ptr(t) if t.numel() else None
+        call("gsat_clf_log_counts", some(self.logits), some(self.y), ptr(self.state), self.max_graphs, self.logit_cols, self.y_cols,
+             self.mode, ptr(self._out), stream())
+        logits, y = self.logits[:n], self.y[:n]
+        nan = torch.full((1,), float("nan"), dtype=torch.float64, device=dev)
+        # the accuracy is formed where classifier_accuracy forms it -- integer hits, one fp64 division on the device -- so the two agree
+        # bit for bit on the same rows
+        C = 2 if self.mode == 0 else self.logit_cols
+        hits = self._out.view(C, 5)[:, (0, 3)].sum() if self.mode == 2 else self._out[:C * C].view(C, C).diagonal().sum()
+        total = n * (C if self.mode == 2 else 1)
+        floats = [self.loss_sum / float(nb), (hits.double() / float(total)).view(1) if total else nan]
+        if self.mode == 2:
+            roc, per_task = classifier_rocauc_tasks(logits, y) if n else (nan, nan.repeat(self.logit_cols))
+            floats += [roc.view(1), per_task]
+        elif self.mode == 0:
+            floats.append(classifier_rocauc(logits, y).view(1) if n else nan)
+        else:
+            floats.append(torch.zeros(1, dtype=torch.float64, device=dev))
+        packed = torch.cat([self._out] + [t.view(torch.int64) for t in floats]).cpu().numpy()   # the second host read
+        counts, fl = packed[:self._words], packed[self._words:].view(np.float64)
+        res = {"n": int(n), "loss": float(fl[0]), "clf_acc": float(fl[1]), "clf_roc": float(fl[2])}
+        if self.mode == 2:
+            c = counts.reshape(C, 5)
+            res.update(task_counts=c[:, :4].copy(), unlabelled=c[:, 4].copy(), clf_roc_tasks=fl[3:3 + C].copy())
+        else:
+            res.update(confusion=counts[:C * C].reshape(C, C).copy(), bad=int(counts[C * C]))
+        return res

@@ -18,7 +18,7 @@ import torch
 from . import explain as _explain
 from ._lib import call, ptr, stream
 from .collate import collate_padded_pair
-from .eval_log import EpochLog, FidelityCurveLog, FidelityLog
+from .eval_log import ClfLog, EpochLog, FidelityCurveLog, FidelityLog
 from .evaluate import MAX_BINS
 from .graph_index import clear_cache, get_index, set_sync_free, sync_free
 from .gsat import get_r
@@ -72,16 +72,19 @@ def _forward_mode(model, evaluating):
     """``sync_loss_dict`` off (the loss dict stays on the device) and, ``evaluating``, every module in ``eval()``; both are put back on
     exit.  What an evaluator's eager tail runs under."""
     modes = [(m, m.training) for m in model.modules()] if evaluating else []
-    was_loss_dict = model.sync_loss_dict
+    has_loss_dict = hasattr(model, "sync_loss_dict")          # a bare backbone (the classifier classes) has no loss dict
+    was_loss_dict = model.sync_loss_dict if has_loss_dict else None
     if evaluating:
         model.eval()
-    model.sync_loss_dict = False
+    if has_loss_dict:
+        model.sync_loss_dict = False
     try:
         yield
     finally:
         for m, t in modes:
             m.training = t
-        model.sync_loss_dict = was_loss_dict
+        if has_loss_dict:
+            model.sync_loss_dict = was_loss_dict
 
 
 @contextmanager
@@ -774,6 +777,188 @@ class ReplayedDualEval(_Replayed):
         ``dual_avg_bkg_att_weights`` of the dual attention.  Ragged: the ids are packed by ``batches`` and every batch is a replay."""
         self._set_seed_state(int(epoch) << 32)
         return _run_epoch(self, graph_ids, epoch)
+
+
+# ---- the classifier alone: ERM pre-training and its evaluation ------------------------------------------------------------------------------
+@contextmanager
+def _module_modes(model, training):
+    """Every module of ``model`` in ``train()`` or ``eval()`` mode inside the block; the flags are put back on exit."""
+    modes = [(m, m.training) for m in model.modules()]
+    model.train(training)
+    try:
+        yield
+    finally:
+        for m, t in modes:
+            m.training = t
+
+
+def _clf_forward(model, criterion, b):
+    """``model(x, edge_index, batch, edge_attr)`` -- no attention -- and the criterion, on a collated batch.  A padded batch runs inside
+    ``padded(b.valid, capacity)`` and its criterion follows the rule of ``GSAT._forward_pass``: the static slice ``[:B]``; ragged, or with a
+    ``capturable`` criterion, the count of real graphs from ``valid`` on the device.  Returns (logits, loss)."""
+    valid = getattr(b, "valid", None)
+    if valid is None:
+        logits = model(b.x, b.edge_index, b.batch, edge_attr=b.edge_attr)
+        return logits, criterion(logits, b.y)
+    N = int(b.x.shape[0])
+    with padded(valid, (N, int(b.edge_index.shape[1]))):
+        get_index(b.edge_index, N).graphs(b.batch, int(b.num_graphs))       # primes the segment cache without batch.max() (a sync)
+        logits = model(b.x, b.edge_index, b.batch, edge_attr=b.edge_attr)
+        B = int(b.num_graphs) - 1                                           # the padding graph is the last one
+        g_valid = valid[2:3] if getattr(b, "ragged", False) else None
+        if g_valid is None and getattr(criterion, "capturable", False):
+            g_valid = valid[2:3] * (1 - valid[3:4])                         # a fixed-count batch keeps B in valid[2] when it overflows
+        loss = criterion(logits[:B], b.y[:B]) if g_valid is None else criterion(logits[:B], b.y[:B], g_valid=g_valid)
+    return logits, loss
+
+
+def _new_clf_log(rs, logits, max_graphs, max_batches):
+    """The ``ClfLog`` of a classifier class whose forward gives ``logits``; the capacities default to the dataset's graph count and to
+    the most batches an epoch over it can have (budget batching may close a batch after any graph)."""
+    ds = rs._datasets[0]
+    y_cols = int(ds.y_all.numel() // max(int(ds.y_all.shape[0]), 1))
+    mg = ds.num_graphs if max_graphs is None else int(max_graphs)
+    most = (mg if rs.ragged else -(-mg // rs.batch_size)) if max_batches is None else int(max_batches)
+    return ClfLog(mg, max(most, 1), int(logits.shape[1]), y_cols, _multi_label(rs.criterion), ds.x_all.device)
+
+
+def _clf_refusals(name, model, criterion, dataset):
+    if hasattr(model, "forward_pass"):
+        raise ValueError(f"{name} replays a bare backbone (get_model); a GSAT model is ReplayedStep's / ReplayedEval's")
+    _refuse_uncapturable(criterion)
+    _refuse_sync_group(model)
+    if getattr(dataset, "y_all", None) is None:
+        raise ValueError(f"{name} needs a dataset with graph labels (y_all)")
+
+
+class _ReplayedClf(_Replayed):
+    """``_Replayed`` for a bare classifier: no attention, so no r schedule -- the static ``r`` stays 0 and nothing reads it."""
+
+    def _r_of(self, epoch):
+        return 0.0
+
+    def step(self, graph_ids, epoch: int = 0) -> Optional[torch.Tensor]:
+        """One replay on the graphs ``graph_ids`` (exactly ``batch_size`` ids -- ragged: 1 to ``batch_size``, or a row of ``batches``).
+        ``epoch`` is accepted and ignored: the classifier has no schedule.  Nothing is read back; returns the device loss."""
+        return super().step(graph_ids, 0)
+
+
+class ReplayedClfStep(_ReplayedClf):
+    """``ReplayedClfStep(model, criterion, optimizer, dataset, batch_size, capacity=None, graph=None, ragged=False, log=False,
+    max_graphs=None, max_batches=None)``: the ERM training step of src/pretrain_clf.py (``train_one_batch``) on a bare backbone
+    (``get_model``) as replays of ONE captured hipGraph.  The graph holds clear_cache, ``collate_padded(..., ragged=)``, inside
+    ``padded(b.valid, capacity)`` the forward ``model(b.x, b.edge_index, b.batch, edge_attr=b.edge_attr)`` in training mode, the
+    criterion, ``zero_grad(set_to_none=True)``, backward and ``optimizer.step()``.  The criterion sees the static slice ``[:B]`` of a
+    fixed-count batch; ragged, or when it is ``capturable``, it reads the count of real graphs from ``valid`` on the device.  Three
+    warm-up runs on a side stream precede the capture; parameters, buffers and optimizer state are put back afterwards, so
+    constructing it does not train.  The modules' training flags are those of the caller outside ``run_once``.
+
+    The learning rate: ``torch.optim.Adam(params, lr=torch.tensor(1e-3, device=dev), capturable=True, fused=True)`` keeps it in a device
+    tensor that the graph reads on every replay, so filling it between replays (an LR scheduler does) changes the update.  A float
+    ``lr`` is frozen into the graph at capture.
+
+    ``ragged``, ``capacity``, ``batches``, ``check_epoch``, ``overflowed()``: as in ``ReplayedStep``.  An overflow batch of a ragged
+    instance has no filled slot: its loss is exactly 0.
+
+    ``log=True``: the body ends in ``log.append`` (a :class:`~dp_gsat_amd.eval_log.ClfLog`, ``max_graphs`` / ``max_batches`` default to
+    the dataset's graph count and the most batches an epoch can have) of the step's logits and loss -- two more launches.
+    ``begin_epoch()`` empties the log and ``epoch_scores()`` is ``log.compute()``: the training accuracy / ROC-AUC and mean loss of
+    ``run_one_epoch(..., 'train')`` without a second pass.  Logging writes only the log: a run with ``log=True`` trains bit for bit
+    like one without.
+
+    After a step: ``loss`` (device scalar), ``clf_logits`` [B + 1, C] and ``batch`` (the PaddedBatch), overwritten by the next replay.
+
+    Refused with ValueError before anything is captured: an optimizer that is not capturable, a multi-label criterion not constructed
+    with ``capturable=True``, ``sync_group`` BatchNorm, a dataset without ``y_all``, a GSAT model, and a capacity the warm-up batch
+    does not fit."""
+
+    def __init__(self, model, criterion, optimizer, dataset, batch_size: int, capacity: Optional[tuple] = None, graph=None,
+                 ragged: bool = False, log: bool = False, max_graphs: Optional[int] = None, max_batches: Optional[int] = None):
+        _need_capturable(optimizer, "ReplayedClfStep needs a capturable optimizer")
+        _clf_refusals("ReplayedClfStep", model, criterion, dataset)
+        self.model, self.criterion, self.optimizer, self.dataset = model, criterion, optimizer, dataset
+        self._setup(model, (dataset,), batch_size, capacity, graph, ragged)
+        self._log_sizes = (max_graphs, max_batches) if log else None
+        self.log = self.batch = self.loss = self.clf_logits = None
+        _capture_training(self, (optimizer,))
+
+    def run_once(self):
+        """The step body (what the graph holds), run on the current stream."""
+        clear_cache()
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        self._overflow.bitwise_or_(b.valid[3:4])
+        with _module_modes(self.model, True):
+            logits, loss = _clf_forward(self.model, self.criterion, b)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self.optimizer.step()
+        if self._log_sizes is not None:
+            with torch.no_grad():
+                if self.log is None:            # the first warm-up run
+                    self.log = _new_clf_log(self, logits, *self._log_sizes)
+                self.log.append(b, logits.detach(), loss.detach())
+        self._publish(False, batch=b, loss=loss.detach(), clf_logits=logits.detach())
+
+    def overflowed(self) -> bool:
+        """True if a step since the last call (or since capture) got a batch that did not fit the capacity.  One host read; clears
+        the flag."""
+        return _take_overflow(self)
+
+    def begin_epoch(self) -> None:
+        """Empty the training-pass log on the device; nothing is read.  Without ``log=True`` there is nothing to empty."""
+        _reset_logs(self)
+
+    def epoch_scores(self) -> dict:
+        """``log.compute()`` -- two host reads -- over the steps since ``begin_epoch()``.  ValueError without ``log=True``, before any
+        step, and when a step since ``begin_epoch()`` did not fit the capacity."""
+        if self.log is None:
+            raise ValueError("ReplayedClfStep was constructed without log=True: it keeps no log of the training pass")
+        return self.log.compute()
+
+
+class ReplayedClfEval(_ReplayedClf):
+    """``ReplayedClfEval(model, criterion, dataset, batch_size, capacity=None, ragged=False, max_graphs=None, max_batches=None,
+    graph=None)``: an evaluation epoch of a bare backbone (``eval_one_batch`` of src/pretrain_clf.py) as replays of ONE captured
+    hipGraph that holds clear_cache, collate_padded, the eval-mode forward and the criterion under ``torch.no_grad()``, and
+    ``log.append`` into a :class:`~dp_gsat_amd.eval_log.ClfLog` (``log``).  The graph reads parameters and running statistics where
+    they live, writes none of them and draws from no generator: evaluating between training steps does not change the training run.
+    After a step: ``clf_logits``, ``loss`` and ``batch``.  Refusals: those of ``ReplayedClfStep`` that do not concern an optimizer."""
+
+    def __init__(self, model, criterion, dataset, batch_size: int, capacity: Optional[tuple] = None, ragged: bool = False,
+                 max_graphs: Optional[int] = None, max_batches: Optional[int] = None, graph=None):
+        _clf_refusals("ReplayedClfEval", model, criterion, dataset)
+        self.model, self.criterion, self.dataset = model, criterion, dataset
+        self._setup(model, (dataset,), batch_size, capacity, graph, ragged)
+        self.log = self.batch = self.loss = self.clf_logits = None
+        _capture_evaluator(self, lambda: self._make_log(max_graphs, max_batches))
+
+    def _make_log(self, max_graphs, max_batches):
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        with torch.no_grad():
+            logits = _clf_forward(self.model, self.criterion, b)[0]
+        self.log = _new_clf_log(self, logits, max_graphs, max_batches)
+
+    def _forward(self, b, epoch=0):
+        """Append the eval-mode forward of batch ``b`` (padded or not) to the log; the modules are in eval mode."""
+        with torch.no_grad():
+            logits, loss = _clf_forward(self.model, self.criterion, b)
+            self.log.append(b, logits, loss)
+        return logits, loss
+
+    def run_once(self):
+        """The body of the captured graph, run on the current stream."""
+        clear_cache()
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        with _module_modes(self.model, False):
+            logits, loss = self._forward(b)
+        self._publish(False, clf_logits=logits, loss=loss, batch=b)
+
+    def run(self, graph_ids, epoch: int = 0) -> dict:
+        """One evaluation epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is a replay, the
+        tail of fewer than ``batch_size`` graphs runs eagerly (``dataset.collate``, the same eval-mode forward, the same append), and
+        ``log.compute()`` -- two host reads -- gives the scores.  Ragged: the ids are packed by ``batches`` and every batch is a
+        replay."""
+        return _run_epoch(self, graph_ids, 0)
 
 
 # ---- explanation fidelity ---------------------------------------------------------------------------------------------------------------------

@@ -36,10 +36,15 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
     the edges among them, and each level line also shows the fraction of nodes kept.  The class refuses ``--fidelity-unit node`` for a
     model that learns edge attention, and the example passes that refusal through.
 
+  * ``--graph [--ragged] --pretrain N`` -- ``from_scratch: false`` of the reference (src/run_gsat.py:984-1007): the backbone is first
+    trained alone for N epochs by ``dp_gsat_amd.pretrain_clf`` (ERM, every batch a replay, the training scores from a device log), one
+    line per epoch; GSAT then starts from that backbone with a fresh optimizer over extractor + backbone.
+
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --train-scores
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --pretrain 10
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity 5
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity-curve 0.2,0.5,0.8
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --node-attention --fidelity-curve 0.2,0.5,0.8 --fidelity-unit node
@@ -101,6 +106,8 @@ def main():
                     help="with --graph: print the fidelity of the top-ratio explanation on the test split at every ratio (increasing, in (0, 1])")
     ap.add_argument("--fidelity-unit", default="edge", choices=["edge", "node"],
                     help="with --fidelity-curve: rank and remove edges, or the nodes of a --node-attention model")
+    ap.add_argument("--pretrain", type=int, default=0, metavar="N",
+                    help="with --graph: pre-train the backbone alone for N epochs (pretrain_clf) and start GSAT from it")
     ap.add_argument("--node-attention", action="store_true", help="learn node attention (learn_edge_att=False) instead of edge attention")
     args = ap.parse_args()
 
@@ -115,6 +122,8 @@ def main():
         ap.error("--fidelity replays a captured fidelity batch: it needs --graph")
     if args.fidelity_curve is not None and not args.graph:
         ap.error("--fidelity-curve replays a captured stacked batch: it needs --graph")
+    if args.pretrain and not args.graph:
+        ap.error("--pretrain replays the classifier step: it needs --graph")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     if world > 1:
@@ -136,6 +145,18 @@ def main():
                aggregators=["mean", "min", "max", "std", "sum"], scalers=False, deg=deg)
     clf = G.get_model(10, 0, 2, False, cfg, dev)
     ext = G.ExtractorMLP(args.hidden, not args.node_attention).to(dev)
+    if args.pretrain > 0:
+        # from_scratch: false -- ERM on the backbone alone, then the GSAT optimizer below over extractor + backbone (run_gsat.py:1005-1007)
+        n_valid = max(1, (len(graphs) - n_train) // 2)
+        splits = {"train": np.arange(n_train), "valid": np.arange(n_train, n_train + n_valid), "test": np.arange(n_train + n_valid, len(graphs))}
+        slots = min(args.batch_size, n_train)
+        pre_opt = torch.optim.Adam(clf.parameters(), lr=torch.tensor(1e-3, device=dev), weight_decay=3e-6, capturable=True, fused=True)
+        best, history = G.pretrain_clf(clf, G.Criterion(2, False), pre_opt, ds, splits, args.pretrain, slots, ragged=args.ragged)
+        for r in history:
+            print(f"pretrain epoch {r['epoch'] + 1:3d}  train loss {r['train_loss']:.4f}  train acc {r['train']:.3f}  "
+                  f"valid acc {r['valid']:.3f}  test acc {r['test']:.3f}", flush=True)
+        print(f"pretrain best epoch {best['metric/best_clf_epoch'] + 1}  valid acc {best['metric/best_clf_valid']:.3f}  "
+              f"test acc {best['metric/best_clf_test']:.3f}", flush=True)
     params = list(clf.parameters()) + list(ext.parameters())
     opt = torch.optim.Adam(params, lr=1e-3, weight_decay=3e-6, **(dict(capturable=True, fused=True) if args.graph else {}))
     gsat = G.GSAT(clf, ext, G.Criterion(2, False), opt, learn_edge_att=not args.node_attention)

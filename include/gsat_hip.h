@@ -1033,6 +1033,45 @@ size_t gsat_delta_kl_segments_workspace_bytes(int64_t num_segments, int64_t max_
 int gsat_delta_kl_segments(const float* att, const uint8_t* label, const int64_t* seg_ptr, int64_t num_segments, int64_t num_edges,
                            int64_t max_seg_len, double eps, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ================================= classifier epoch log ===================================== */
+
+/*
+ * Appends one batch to a device-resident log of a classifier epoch, at the offsets held in log_state int64[4] = (graphs logged,
+ * batches logged, flags, 0) ON THE DEVICE; two launches (the copies, then one thread that commits), nothing read back, no memset,
+ * launch geometry from graph_cap only (capturable, kernels only).
+ * The batch: logits fp32[graph_cap, logit_cols] and y fp32[graph_cap, y_cols] (NaN = unlabelled, kept); valid int32[4] = (N_real,
+ * E_real, B, overflow) of gsat_collate_padded, nullable: without it all graph_cap rows are logged, with it the first B = valid[2];
+ * rows at or beyond the count are never loaded; loss fp32[1], nullable.  With (g0, b0) the counts in log_state:
+ *   log_logits / log_y rows g0 .. g0 + B - 1 = the first B rows
+ *   log_loss_sum double[1]                   += loss[0], or turns NaN when loss is null
+ * and then log_state = (g0 + B, b0 + 1, flags, 0).  B = 0 is a legal append: a batch with no rows.  A batch whose valid[3] is set
+ * appends nothing and sets flag bit 0; a count outside [0, graph_cap], or an append that would exceed max_graphs or max_batches,
+ * appends nothing and sets flag bit 1.  A flagged append writes nothing but its flag.  max_graphs < 2^31 (GSAT_ERR_UNSUPPORTED).
+ * replaces: the host lists all_clf_labels / all_clf_logits / all_loss of run_one_epoch (src/pretrain_clf.py:75-91).
+ */
+int gsat_clf_log_append(const float* logits, const float* y, const int32_t* valid, const float* loss, int64_t graph_cap,
+                        int64_t logit_cols, int64_t y_cols, float* log_logits, float* log_y, double* log_loss_sum, int64_t* log_state,
+                        int64_t max_graphs, int64_t max_batches, void* stream);
+
+/*
+ * out int64[gsat_clf_log_counts_words(logit_cols, y_cols, mode)]: integer counts over the first clamp(log_state[0], 0, max_graphs)
+ * logged rows, read in the kernel; the grid is sized from max_graphs.  The call zeroes out itself (a launch ahead of the counting
+ * one).  Comparisons only, 64-bit integer atomics: order independent, bitwise repeatable.  mode as in gsat_criterion_fwd:
+ *   0 binary, logit_cols == y_cols == 1: the predicted class is z > 0;
+ *   1 multi-class, C = logit_cols in [2, 32], y_cols == 1: the predicted class is the argmax, the LOWEST index on ties;
+ *   2 multi-label, T = logit_cols == y_cols in [1, 256]: the prediction of every (row, task) entry is z > 0 (a NaN logit predicts 0).
+ * modes 0 and 1: out = confusion[C][C] (C = 2 in mode 0; row = label, column = prediction), then one counter `bad`: the rows whose
+ * label is not an integer in [0, C) or whose logits hold a NaN; they match nothing, as in torch's preds == labels.
+ * mode 2: out = [T][5]: per task (tn, fp, fn, tp) over its labelled entries (label 0 = negative, anything else positive) and the
+ * number of its unlabelled (NaN) entries.
+ * More classes or tasks: GSAT_ERR_UNSUPPORTED (and gsat_clf_log_counts_words gives -1, as for columns a mode does not take).
+ * z > 0 differs from get_preds's sigmoid(z) > 0.5 only where the fp32 sigmoid rounds to exactly 0.5 for z > 0: z below about 1e-7.
+ * replaces: get_preds and the accuracy of eval_one_batch / get_eval_score (src/pretrain_clf.py:93-100).
+ */
+int64_t gsat_clf_log_counts_words(int64_t logit_cols, int64_t y_cols, int mode);
+int gsat_clf_log_counts(const float* log_logits, const float* log_y, const int64_t* log_state, int64_t max_graphs, int64_t logit_cols,
+                        int64_t y_cols, int mode, int64_t* out, void* stream);
+
 /* ================================= explanation fidelity log ================================= */
 
 /*
