@@ -27,6 +27,8 @@ SIGNATURES = {
     "gsat_reverse_edge_perm": (INT, [P, I64, I64, P, P, P, SZ, P]),
     "gsat_reverse_edge_perm_csr": (INT, [P, P, P, P, P, P, P, P, I64, I64, P, P, P]),
     "gsat_segment_ptr": (INT, [P, I64, I64, P, P, P]),
+    "gsat_csr_counting_limits": (None, [P]),
+    "gsat_csr_counts": (INT, [I64]),
     "gsat_gather_i64": (INT, [P, I64, P, I64, P, P]),
     "gsat_row_chunks_workspace_bytes": (SZ, [I64]),
     "gsat_row_chunks": (INT, [P, I64, P, P, SZ, P]),

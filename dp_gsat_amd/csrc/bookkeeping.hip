@@ -745,6 +745,14 @@ int gsat_segment_ptr32(const int64_t* seg_ids, int64_t n, int64_t num_seg, int32
     return GSAT_OK;
 }
 
+void gsat_csr_counting_limits(int64_t out[3]) {
+    out[0] = COUNT_ELEM_ROW;
+    out[1] = COUNT_CHUNK;
+    out[2] = GSAT_COUNTING_MAX_KEYS;
+}
+
+int gsat_csr_counts(int64_t keys) { return counting_build(keys / 2) ? 1 : 0; }      // as gsat_build_csr asks; the pair build has 2E keys
+
 int gsat_gather_i64(const int64_t* table, int64_t table_len, const int64_t* index, int64_t n, int64_t* out, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     GSAT_REQUIRE(n >= 0 && table_len >= 0, GSAT_ERR_ARG, "gsat_gather_i64: bad n");

@@ -115,6 +115,16 @@ int gsat_segment_ptr(const int64_t* seg_ids, int64_t num_rows, int64_t num_segme
 int gsat_segment_ptr32(const int64_t* seg_ids, int64_t n, int64_t num_segments, int32_t* ptr, int32_t* seg_ids32,
                        int32_t* flags, void* stream);
 
+/*
+ * Which build the CSR entry points take (host only, no device work).  Up to out[2] keys they count (count / scan / place / order),
+ * above that, or with GSAT_CSR_COUNTING=0 in the environment, they sort with rocPRIM; both give the same arrays.
+ * gsat_csr_counting_limits: out[0] = longest row ordered one thread per entry, out[1] = entries per LDS chunk of a longer row,
+ * out[2] = the key limit.  gsat_csr_counts(keys): 1 if a build of that many keys counts, 0 if it sorts; gsat_build_csr has
+ * num_edges keys, gsat_build_csr_pair 2 * E.
+ */
+void gsat_csr_counting_limits(int64_t out[3]);
+int gsat_csr_counts(int64_t keys);
+
 /* out[e] = batch[index[e]]  (edge -> graph id, `batch[col]` of example/gsat.py:136). int64 out; index values outside
  * [0, table_len) are clamped into the table (they are counted as range errors by the CSR builders). */
 int gsat_gather_i64(const int64_t* table, int64_t table_len, const int64_t* index, int64_t n, int64_t* out, void* stream);
