@@ -196,6 +196,12 @@ def pna_aggregate(x: Tensor, edge_index: Tensor, edge_atten: Optional[Tensor], a
     m = torch.cat(parts, dim=-1)
     if edge_atten is not None:
         m = m * edge_atten
+    return pna_aggregate_messages(m, dst, N, aggregators, scalers, avg_deg)
+
+
+def pna_aggregate_messages(m: Tensor, dst: Tensor, N: int, aggregators: List[str], scalers: List[str],
+                           avg_deg: Dict[str, float]) -> Tensor:
+    """PNAConvSimple.aggregate (src/models/conv_layers.py:178-185, 193-259) of the messages ``m`` [E, F] arriving at ``dst``."""
     outs = []
     for a in aggregators:                                                   # :179
         if a == "sum":

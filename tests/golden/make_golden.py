@@ -9,8 +9,9 @@
    source is read or copied.
 2. oracle_*.npz -- inputs and outputs of the CPU oracle (oracle/) on small seeded cases.  They pin the
    oracle against silent drift (tests/test_oracle_golden.py) and give the GPU parity tests fixed targets
-   (tests/test_gpu_golden.py).  They are NOT outputs of the reference: PyG / torch-scatter / torch-sparse
-   are not installed, so the reference cannot run here (parity unpinned at that boundary, see oracle/__init__.py).
+   (tests/test_gpu_models.py).  They are NOT outputs of the reference.  Outputs of the reference's own classes
+   are the ref_* files next to them, written by oracle/record_reference.py (see its docstring and DESIGN.md
+   section 3); this script does not touch them.
 """
 import json
 import os
