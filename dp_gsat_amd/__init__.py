@@ -34,6 +34,8 @@ from .eval_log import EpochLog, FidelityCurveLog, FidelityLog, delta_kl_segments
 from .eval_log import ClfLog
 from .replay import ReplayedClfEval, ReplayedClfStep
 from .pretrain import pretrain_clf, update_best_clf
+from .explain import (LevelComponents, component_labels, components_lds_cap, explanation_connectivity, largest_component_mask, level_components,
+                      level_components_reset)
 
 __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "get_preds", "GINConv", "GINEConv",
            "PNAConvSimple", "GIN", "PNA", "GSAT", "ExtractorMLP", "concrete_sample", "get_r", "gumbel_sigmoid",
@@ -49,4 +51,5 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "ReplayedFidelityCurve", "explanation_stack_multi", "explanation_fidelity_curves", "level_overlap",
            "ReplayedDualFidelityCurve", "NodeRanking", "rank_nodes", "topk_node_mask", "node_levels", "node_precision_at_k",
            "explanation_node_subgraph", "explanation_stack_nodes", "explanation_node_fidelity_curve",
-           "ClfLog", "ReplayedClfStep", "ReplayedClfEval", "pretrain_clf", "update_best_clf"]
+           "ClfLog", "ReplayedClfStep", "ReplayedClfEval", "pretrain_clf", "update_best_clf", "LevelComponents", "components_lds_cap",
+           "level_components", "level_components_reset", "largest_component_mask", "component_labels", "explanation_connectivity"]

@@ -166,6 +166,10 @@ SIGNATURES = {
     "gsat_level_overlap_reset": (INT, [P, I64, P]),
     "gsat_fidelity_stack_nodes_workspace_bytes": (SZ, [I64, I64, I64]),
     "gsat_fidelity_stack_nodes": (INT, [P, I64, I64, P, I64, P, P, I64, I64, I64, P, P, P, P, P, P, P, SZ, P]),
+    "gsat_level_components_lds_cap": (I64, []),
+    "gsat_level_components_wave_nodes": (I64, []),
+    "gsat_level_components": (INT, [P, I64, I64, P, P, P, I64, P, I64, I64, P, P, P, P, P, P]),
+    "gsat_level_components_reset": (INT, [P, I64, P]),
 }
 
 

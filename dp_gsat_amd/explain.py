@@ -231,6 +231,178 @@ def level_overlap_reset(out: torch.Tensor) -> None:
     call("gsat_level_overlap_reset", ptr(out), int(out.shape[0]), stream())
 
 
+# ---- connectivity: components of the kept edges per graph and level (csrc/components.hip) -----------------------------------------------------
+class LevelComponents(NamedTuple):
+    """out int64[S, 8]: the accumulator; per_graph int32[G, S, 5]: (components, kept, big_edges, touched, big_nodes) per looked-at graph
+    and level, -1 rows for a skipped graph, 0 rows for a graph that was not looked at (or None); node_comp int32[N] / edge_big bool[E]
+    of the LAST level (or None): the smallest node id of the node's component, -1 for an untouched node or a graph that was not looked
+    at; whether the edge lies in its graph's largest component by kept edges."""
+    out: torch.Tensor
+    per_graph: Optional[torch.Tensor]
+    node_comp: Optional[torch.Tensor]
+    edge_big: Optional[torch.Tensor]
+
+
+def components_lds_cap() -> int:
+    """Largest graph (in NODES) gsat_level_components takes; there is no path for larger graphs."""
+    return int(_lib.load().gsat_level_components_lds_cap())
+
+
+def components_wave_nodes() -> int:
+    """Largest graph (in nodes) one wavefront of gsat_level_components takes; a larger one is the whole workgroup's."""
+    return int(_lib.load().gsat_level_components_wave_nodes())
+
+
+def _check_valid(valid):
+    if valid is None:
+        return None
+    if not isinstance(valid, torch.Tensor) or valid.dtype != torch.int32 or valid.numel() < 4 or not valid.is_cuda:
+        raise ValueError("valid must be an int32 ROCm tensor (N_real, E_real, B, overflow)")
+    return valid.contiguous()
+
+
+def level_components(edge_index, batch, level, S: int, *, num_graphs: Optional[int] = None, max_seg_nodes: Optional[int] = None,
+                     ranked_graphs: Optional[int] = None, valid=None, out=None, per_graph: bool = False, labels: bool = False):
+    """Connected components of every graph's kept edges at every level of a fidelity curve (gsat_level_components): ADDS into ``out``
+    int64[S, 8] on the device -- a fresh block zeroed by the reset kernel when ``out`` is None -- per level ``s`` and counted graph
+    ``(1, components, kept, big_edges, touched, big_nodes, components == 1, 0)``; ``out[0, 7]`` counts the skipped graphs.  ``level``:
+    uint8[E] from :func:`explanation_levels` with the same ``S`` levels; level ``s`` keeps the edges with ``level <= s``.  Direction is
+    ignored, a self-loop joins nothing, the touched nodes of a level are the endpoints of its kept edges.
+
+    Returns ``out``, or with ``per_graph`` / ``labels`` a :class:`LevelComponents` that also holds ``per_graph`` int32[G, S, 5] and the
+    last level's ``node_comp`` int32[N] and ``edge_big`` bool[E] (ties between equally large components go to the smaller label).
+
+    ``max_seg_nodes`` (keyword only): a bound on the NODES of one graph that the caller knows, e.g. from its dataset; above
+    :func:`components_lds_cap` it is a ValueError, and a graph that exceeds a wrong bound is skipped whole (-1 rows, ``out[0, 7]``),
+    never cut.  Without it the batch index's largest node count is read back once (cached) -- a ValueError in sync-free mode and under
+    capture.  ``ranked_graphs``: look at the first so many graphs only -- for a padded batch its ``num_graphs - 1``, so that the padding
+    graph is never touched.  ``valid``: the int32[4] word of a padded batch -- only graphs below ``valid[2]`` count, edges at or beyond
+    ``valid[1]`` are never loaded, nothing is added when ``valid[3]`` is set.  One launch (two with the zeroing; the outputs asked for
+    are filled first), integer and exact, nothing read back: capturable with ``max_seg_nodes``."""
+    if isinstance(S, bool) or int(S) != S or not 1 <= int(S) <= MAX_LEVELS:
+        raise ValueError(f"level_components takes 1 to {MAX_LEVELS} levels")
+    S = int(S)
+    if not isinstance(level, torch.Tensor) or level.dtype != torch.uint8:
+        raise ValueError("level must be a uint8 tensor (explanation_levels)")
+    if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
+        raise ValueError("edge_index must be an int64 tensor of shape [2, E]")
+    E = int(edge_index.shape[1])
+    if level.numel() != E:
+        raise ValueError(f"level has {level.numel()} entries for {E} edges")
+    if max_seg_nodes is not None:
+        if isinstance(max_seg_nodes, bool) or int(max_seg_nodes) != max_seg_nodes or not 0 <= int(max_seg_nodes) <= components_lds_cap():
+            raise ValueError(f"max_seg_nodes = {max_seg_nodes} is outside [0, components_lds_cap() = {components_lds_cap()}]: the "
+                             "components kernel cannot take it, and a declared bound never changes behaviour silently")
+        max_seg_nodes = int(max_seg_nodes)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (S, 8)
+                            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int64 ROCm tensor of shape [{S}, 8]")
+    for t in (edge_index, batch, level) + ((out,) if out is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    valid = _check_valid(valid)
+    if max_seg_nodes is None and (sync_free() or torch.cuda.is_current_stream_capturing()):
+        raise ValueError("level_components without max_seg_nodes would read the batch's largest node count back: give the bound in "
+                         "sync-free mode and under capture")
+    seg = _segments(edge_index, batch, num_graphs)
+    G, N, dev = seg.G, seg.index.N, edge_index.device
+    if max_seg_nodes is None:
+        max_seg_nodes = seg.max_nodes_per_graph
+        if max_seg_nodes > components_lds_cap():
+            raise ValueError(f"the batch's largest graph has {max_seg_nodes} nodes, above components_lds_cap() = {components_lds_cap()}")
+    if ranked_graphs is not None:
+        if isinstance(ranked_graphs, bool) or not 0 <= int(ranked_graphs) <= G:
+            raise ValueError(f"ranked_graphs = {ranked_graphs} outside [0, {G}]")
+        G = int(ranked_graphs)
+    eptr, eorder = seg.edge_segments[:2]
+    lv = level.reshape(-1).contiguous()
+    fresh = out is None
+    if fresh:
+        out = torch.empty((S, 8), dtype=torch.int64, device=dev)
+        call("gsat_level_components_reset", ptr(out), S, stream())
+    pg = torch.zeros((G, S, 5), dtype=torch.int32, device=dev) if per_graph else None
+    node_comp = torch.full((N,), -1, dtype=torch.int32, device=dev) if labels else None
+    edge_big = torch.zeros(E, dtype=torch.uint8, device=dev) if labels else None
+    some = lambda t: ptr(t) if t is not None and t.numel() else None
+    call("gsat_level_components", some(seg.index.edge_index), E, N, ptr(seg.node_ptr), ptr(eptr), some(eorder), G, some(lv), S,
+         max_seg_nodes, ptr(valid) if valid is not None else None, some(pg), ptr(out), some(node_comp), some(edge_big), stream())
+    if not (per_graph or labels):
+        return out
+    return LevelComponents(out, pg, node_comp, edge_big.bool() if labels else None)
+
+
+def level_components_reset(out: torch.Tensor) -> None:
+    """Zero an accumulator of :func:`level_components` by a kernel (no memset node, so a captured graph may hold it)."""
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or out.dim() != 2 or int(out.shape[1]) != 8 or not out.is_cuda \
+            or not out.is_contiguous():
+        raise ValueError("out must be a contiguous int64 ROCm tensor of shape [S, 8]")
+    call("gsat_level_components_reset", ptr(out), int(out.shape[0]), stream())
+
+
+def _mask_level(edge_mask, E: int) -> torch.Tensor:
+    """uint8[E] levels of a one-level curve whose level 0 keeps the edges of ``edge_mask``: 0 where it is set, 1 elsewhere."""
+    if not isinstance(edge_mask, torch.Tensor) or edge_mask.dtype not in (torch.bool, torch.uint8) or edge_mask.numel() != E:
+        raise ValueError(f"edge_mask must be a bool or uint8 tensor with one entry for each of the {E} edges")
+    if not edge_mask.is_cuda:
+        raise GsatHipError("dp_gsat_amd.explain needs ROCm (cuda) tensors: the HIP path has no CPU fallback")
+    return (edge_mask.reshape(-1) == 0).to(torch.uint8)
+
+
+def largest_component_mask(edge_index, batch, edge_mask, *, num_graphs: Optional[int] = None, max_seg_nodes: Optional[int] = None,
+                           ranked_graphs: Optional[int] = None, valid=None) -> torch.Tensor:
+    """bool[E]: the edges of ``edge_mask`` that lie in their graph's largest connected component by kept edges (ties: the component with
+    the smaller smallest node id) -- :func:`level_components` with one level.  False at the edges of graphs that are not looked at or
+    are skipped.  The keywords are those of :func:`level_components`."""
+    lv = _mask_level(edge_mask, int(edge_index.shape[1]))
+    return level_components(edge_index, batch, lv, 1, num_graphs=num_graphs, max_seg_nodes=max_seg_nodes, ranked_graphs=ranked_graphs,
+                            valid=valid, labels=True).edge_big
+
+
+def component_labels(edge_index, batch, edge_mask, *, num_graphs: Optional[int] = None, max_seg_nodes: Optional[int] = None,
+                     ranked_graphs: Optional[int] = None, valid=None) -> torch.Tensor:
+    """int32[N]: for every node the smallest node id (batch-global) of its connected component under the edges of ``edge_mask``, -1 for
+    a node no kept edge touches (and for graphs that are not looked at or are skipped).  The keywords are those of
+    :func:`level_components`."""
+    lv = _mask_level(edge_mask, int(edge_index.shape[1]))
+    return level_components(edge_index, batch, lv, 1, num_graphs=num_graphs, max_seg_nodes=max_seg_nodes, ranked_graphs=ranked_graphs,
+                            valid=valid, labels=True).node_comp
+
+
+CONNECTIVITY_KEYS = ("components", "largest_edge_share", "largest_node_share", "connected_fraction")
+
+
+def connectivity_scores(counts) -> dict:
+    """The host side of a :func:`level_components` accumulator read back as nested lists ``[S][8]``: lists over the levels --
+    ``components`` (mean per graph), ``largest_edge_share`` (sum of big_edges / sum of kept), ``largest_node_share`` (sum of big_nodes /
+    sum of touched), ``connected_fraction`` (graphs with exactly one component / graphs) -- 0.0 where a denominator is 0, and ``n``,
+    the graphs counted."""
+    ratio = lambda a, b: a / b if b else 0.0
+    return {"components": [ratio(c[1], c[0]) for c in counts], "largest_edge_share": [ratio(c[3], c[2]) for c in counts],
+            "largest_node_share": [ratio(c[5], c[4]) for c in counts], "connected_fraction": [ratio(c[6], c[0]) for c in counts],
+            "n": int(counts[0][0])}
+
+
+def explanation_connectivity(data, att, ks=None, ratios=None) -> dict:
+    """How connected the explanation ``att`` of the batch ``data`` is at the sparsity levels ``ks`` or ``ratios``: one ranking,
+    :func:`explanation_levels`, one :func:`level_components` launch and ONE host read of its 8 S counts (besides the batch index's
+    cached read of its largest graph, which the eager ranking makes anyway).  Returns :func:`connectivity_scores` -- ``components``,
+    ``largest_edge_share``, ``largest_node_share``, ``connected_fraction`` as lists over the levels, ``n`` -- and ``levels``.  ``data``: a
+    ``Batch``, or a ``PaddedBatch`` (its padding graph and empty slots count nothing).  For the baseline of the ground truth itself, pass
+    ``edge_label`` as ``att`` (its labelled edges rank first), or the label mask to :func:`level_components` as a one-level curve."""
+    ks, ratios = check_levels(ks, ratios)
+    S = len(ks if ks is not None else ratios)
+    G = getattr(data, "num_graphs", None)
+    valid = getattr(data, "valid", None)
+    seg = _segments(data.edge_index, data.batch, G)
+    seg.largest_graph()                                    # both maxima in one read: the ranking's bound and the components'
+    level = explanation_levels(att, data.edge_index, data.batch, ks=ks, ratios=ratios, num_graphs=G)
+    out = level_components(data.edge_index, data.batch, level, S, num_graphs=G, valid=valid,
+                           ranked_graphs=seg.G - 1 if valid is not None else None)
+    res = connectivity_scores(out.tolist())               # the one host read
+    res["levels"] = list(ks if ks is not None else ratios)
+    return res
+
+
 def explanation_levels(att, edge_index, batch, ks=None, ratios=None, num_graphs: Optional[int] = None, *,
                        max_seg_edges: Optional[int] = None, ranked_graphs: Optional[int] = None) -> torch.Tensor:
     """uint8[E]: for every edge the smallest level ``s`` whose top-``ks[s]`` (or top-``ceil(ratios[s] * E_g)``) of its graph holds it,

@@ -386,6 +386,7 @@ class GraphSegments:
         self._flags = flags
         self._edge = None
         self._max_edges = None
+        self._max_nodes = None
         self._stream_host = None          # (edge pointers, node pointers, verdict) on the host: stream_plan's one read
         self._stream_plans = {}
 
@@ -458,6 +459,28 @@ class GraphSegments:
             eptr = self.edge_segments[0]
             self._max_edges = int((eptr[1:] - eptr[:-1]).max().item()) if self.G > 0 else 0
         return self._max_edges
+
+    def largest_graph(self) -> tuple:
+        """(max_edges_per_graph, max_nodes_per_graph) with ONE read-back for whichever of the two is not cached yet; (-1, -1) entries
+        while they are unknown and must not be read -- sync-free mode, or during stream capture."""
+        if (self._max_edges is None or self._max_nodes is None) and not (_SYNC_FREE or torch.cuda.is_current_stream_capturing()):
+            if self.G > 0:
+                eptr, nptr = self.edge_segments[0], self.node_ptr
+                self._max_edges, self._max_nodes = (int(v) for v in torch.stack([(eptr[1:] - eptr[:-1]).max(),
+                                                                                 (nptr[1:] - nptr[:-1]).max()]).tolist())
+            else:
+                self._max_edges = self._max_nodes = 0
+        return (-1 if self._max_edges is None else self._max_edges, -1 if self._max_nodes is None else self._max_nodes)
+
+    @property
+    def max_nodes_per_graph(self) -> int:
+        """Node count of the largest graph: one small read-back per batch, cached.  -1 while it is unknown and must not be read."""
+        if self._max_nodes is None:
+            if _SYNC_FREE or torch.cuda.is_current_stream_capturing():
+                return -1
+            self._max_nodes = int((self.node_ptr[1:] - self.node_ptr[:-1]).max().item()) if self.G > 0 else 0
+        return self._max_nodes
+
 
 
 class StreamPlan:

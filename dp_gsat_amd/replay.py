@@ -552,6 +552,25 @@ def _reset_logs(ev):
     for log in (ev.log, getattr(ev, "dual_log", None)):
         if log is not None:
             log.reset()
+    if getattr(ev, "components", None) is not None:
+        _explain.level_components_reset(ev.components)
+
+
+def _max_seg_nodes(dataset, what):
+    """The dataset's largest node count for a captured ``level_components`` (one host read); ValueError above its cap."""
+    n = int(dataset.node_counts.max()) if dataset.num_graphs else 0
+    if n > _explain.components_lds_cap():
+        raise ValueError(f"{what}'s largest graph has {n} nodes, above components_lds_cap() = {_explain.components_lds_cap()}: "
+                         "connectivity=True cannot take it")
+    return n
+
+
+def _components(b, level, S, max_seg_nodes, out):
+    """``level_components`` of the level row ``level`` on the real batch ``b`` (padded: without its padding graph) into ``out``."""
+    valid = getattr(b, "valid", None)
+    G = int(b.num_graphs)
+    _explain.level_components(b.edge_index, b.batch, level, S, num_graphs=G, max_seg_nodes=max_seg_nodes,
+                              ranked_graphs=G - 1 if valid is not None else None, valid=valid, out=out)
 
 
 def _scores(ev):
@@ -1134,14 +1153,24 @@ class ReplayedFidelityCurve(_Replayed):
     graphs ``graph_ids``: computed on the host from the dataset's node counts and the level rule (``min(k, N_g)``, or the same fp64
     ``ceil(N_g * ratio)``), exact, with no device read per batch; ``kept_fraction`` stays the fraction of edges.  Refused besides the above:
     a model that learns edge attention, and a dataset whose largest graph has more NODES than ``rank_edges_lds_cap()`` (its edge counts
-    are not ranked and not bounded)."""
+    are not ranked and not bounded).
+
+    ``connectivity=True`` (``unit="edge"`` only; with ``unit="node"`` a ValueError before capture): the captured body ends in ONE
+    ``level_components`` launch on the real batch -- ``stack.edge_level``, the batch's ``valid``, ``ranked_graphs = num_graphs - 1`` and the
+    dataset's largest node count as ``max_seg_nodes`` (one host read of ``dataset.node_counts`` at construction; above
+    ``components_lds_cap()`` a ValueError there) -- into ``components`` int64[S, 8], which ``run`` resets next to the log and reads once
+    more at the end: it adds ``components``, ``largest_edge_share``, ``largest_node_share`` and ``connected_fraction`` (lists over the
+    levels, ``connectivity_scores``).  Every other returned value is bitwise what it is without the keyword."""
 
     def __init__(self, gsat, dataset, batch_size: int, ks=None, ratios=None, capacity: Optional[tuple] = None,
-                 max_graphs: Optional[int] = None, graph=None, ragged: bool = False, unit: str = "edge"):
+                 max_graphs: Optional[int] = None, graph=None, ragged: bool = False, unit: str = "edge", connectivity: bool = False):
         self.ks, self.ratios = _explain.check_levels(ks, ratios)
         if unit not in ("edge", "node"):
             raise ValueError("unit must be 'edge' or 'node'")
-        self.unit = unit
+        if connectivity and unit != "edge":
+            raise ValueError("connectivity=True scores the kept EDGES of an edge ranking: it goes with unit='edge' only (node-induced "
+                             "variants are a different question)")
+        self.unit, self.connectivity, self.components = unit, bool(connectivity), None
         if hasattr(gsat, "dual_forward_pass") or not hasattr(gsat, "forward_pass"):
             raise ValueError("ReplayedFidelityCurve replays GSAT.forward_pass and its backbone; DualGSAT fidelity is not covered")
         if unit == "node" and gsat.learn_edge_att:
@@ -1163,6 +1192,10 @@ class ReplayedFidelityCurve(_Replayed):
             if self.max_seg_edges > _explain.rank_edges_lds_cap():
                 raise ValueError(f"the dataset's largest graph has {self.max_seg_edges} edges, above rank_edges_lds_cap() = "
                                  f"{_explain.rank_edges_lds_cap()}: the captured ranking takes the fused path only")
+        if self.connectivity:
+            self._cc_nodes = _max_seg_nodes(dataset, "the dataset")                                # one host read, here
+            S = len(self.ks if self.ks is not None else self.ratios)
+            self.components = torch.zeros((S, 8), dtype=torch.int64, device=dataset.x_all.device)
         self.gsat, self.dataset = gsat, dataset
         self._setup(gsat, (dataset,), batch_size, capacity, graph, ragged)
         self._max_graphs = dataset.num_graphs if max_graphs is None else int(max_graphs)
@@ -1198,6 +1231,8 @@ class ReplayedFidelityCurve(_Replayed):
             over = stack.valid[:, 3].amax().view(1)
             self._overflow.bitwise_or_(over if valid is None else over | valid[3:4])
             self.log.append(logits, stack.valid, valid)
+            if self.connectivity:
+                _components(b, stack.edge_level, self.components.shape[0], self._cc_nodes, self.components)
         return att, stack, logits
 
     def run_once(self):
@@ -1219,6 +1254,9 @@ class ReplayedFidelityCurve(_Replayed):
         res = _run_epoch(self, graph_ids, epoch)
         if self.unit == "node":
             res["kept_node_fraction"] = self._kept_node_fraction(graph_ids)
+        if self.connectivity:
+            scores = _explain.connectivity_scores(self.components.tolist())                       # the read of the components block
+            res.update({key: scores[key] for key in _explain.CONNECTIVITY_KEYS})
         return res
 
     def _kept_node_fraction(self, graph_ids) -> list:
@@ -1269,13 +1307,21 @@ class ReplayedDualFidelityCurve(_Replayed):
     Refused with ValueError before anything is captured: bad levels or ``2 * S > 16``; what a padded pair refuses (edge attention, the
     multi-label criterion, ``check_pair``, a capacity that is no triple); ``sync_group`` BatchNorm; a model without ``dual_forward_pass``;
     a primal dataset without graph labels or without ``edge_label`` (the f1 term of ``dual_forward_pass`` needs it); a largest primal
-    graph above ``rank_edges_lds_cap()``."""
+    graph above ``rank_edges_lds_cap()``.
+
+    ``connectivity=True``: two more launches per replay, ``level_components`` of each row of ``stack.edge_level`` on the primal batch, into
+    ``components`` int64[2, S, 8] (reset with the overlap block, read once more by ``run``); the ``primal`` and ``dual`` dicts gain
+    ``components``, ``largest_edge_share``, ``largest_node_share`` and ``connected_fraction`` -- which of the two explanations is the more
+    connected one.  Refused when the primal dataset's largest graph has more nodes than ``components_lds_cap()``.  Every other returned
+    value is bitwise what it is without the keyword."""
 
     def __init__(self, dual_gsat, primal_ds, dual_ds, batch_size: int, ks=None, ratios=None, capacity: Optional[tuple] = None,
-                 max_graphs: Optional[int] = None, seed: Optional[int] = None, graphs=None, ragged: bool = False):
+                 max_graphs: Optional[int] = None, seed: Optional[int] = None, graphs=None, ragged: bool = False,
+                 connectivity: bool = False):
         self.ks, self.ratios = _explain.check_levels(ks, ratios)
         self.levels = tuple(self.ks if self.ks is not None else self.ratios)
         _explain.check_rankings(2, len(self.levels))
+        self.connectivity, self.components = bool(connectivity), None
         m = dual_gsat
         if not hasattr(m, "dual_forward_pass"):
             raise ValueError("ReplayedDualFidelityCurve replays DualGSAT.dual_forward_pass; ReplayedFidelityCurve covers a plain GSAT")
@@ -1298,6 +1344,9 @@ class ReplayedDualFidelityCurve(_Replayed):
         self._max_graphs = primal_ds.num_graphs if max_graphs is None else int(max_graphs)
         self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
         self.overlap = torch.zeros((len(self.levels), 3), dtype=torch.int64, device=dev)
+        if self.connectivity:
+            self._cc_nodes = _max_seg_nodes(primal_ds, "the primal dataset")                       # one host read, here
+            self.components = torch.zeros((2, len(self.levels), 8), dtype=torch.int64, device=dev)
         self.log = self.batch = self.dual_batch = self.edge_att = self.dual_att = self.edge_level = self.stack = self.logits = None
         try:
             with _capture_mode(m, evaluating=True):
@@ -1313,6 +1362,9 @@ class ReplayedDualFidelityCurve(_Replayed):
         if self.log is not None:
             self.log.reset()
         _explain.level_overlap_reset(self.overlap)
+        if self.components is not None:
+            for block in self.components:
+                _explain.level_components_reset(block)
 
     def _make_log(self):
         pb, _ = collate_padded_pair(self.primal_ds, self.dual_ds, self.graph_ids, self.capacity, ragged=self.ragged)
@@ -1351,6 +1403,9 @@ class ReplayedDualFidelityCurve(_Replayed):
         self._overflow.bitwise_or_(over if valid is None else over | valid[3:4])
         self.log.append(logits, stack.valid, valid)
         _explain.level_overlap(stack.edge_level[0], stack.edge_level[1], len(self.levels), valid=valid, out=self.overlap)
+        if self.connectivity:
+            for r in range(2):
+                _components(pb, stack.edge_level[r], len(self.levels), self._cc_nodes, self.components[r])
         return stack, logits
 
     def run_once(self, mixed: bool):
@@ -1387,6 +1442,10 @@ class ReplayedDualFidelityCurve(_Replayed):
         out["jaccard"] = [c[0] / (c[1] + c[2] - c[0]) if c[1] + c[2] - c[0] else 0.0 for c in counts]
         out["overlap"] = [c[0] / min(c[1], c[2]) if min(c[1], c[2]) else 0.0 for c in counts]
         out["p_full"], out["n"] = res["p_full"], res["n"]
+        if self.connectivity:
+            for name, counts in zip(("primal", "dual"), self.components.tolist()):                 # the read of the components block
+                scores = _explain.connectivity_scores(counts)
+                out[name].update({key: scores[key] for key in _explain.CONNECTIVITY_KEYS})
         return out
 
     def overflowed(self) -> bool:

@@ -298,10 +298,12 @@ def node_subgraph_padded(data, node_keep: torch.Tensor, capacity: Tuple[int, int
 
 
 def explanation_subgraph(att, data, k: Optional[int] = None, ratio: Optional[float] = None, complement: bool = False,
-                         drop_isolated: bool = True, path: str = "auto") -> SubgraphBatch:
+                         drop_isolated: bool = True, path: str = "auto", connected: bool = False) -> SubgraphBatch:
     """Every graph's ``k`` (or ``ceil(ratio * E_g)``) highest-attention edges as a batch of their own (``complement``: everything
     BUT those edges); ties as in :mod:`dp_gsat_amd.explain` (lower edge id first).  The kept edges' attention rides along as
-    ``edge_att = att[edge_id]``."""
+    ``edge_att = att[edge_id]``.  ``connected=True``: the mask is replaced by its largest connected component in every graph before the
+    extraction (:func:`~dp_gsat_amd.explain.largest_component_mask`: most kept edges, ties to the component with the smaller smallest
+    node id) -- the explanation as ONE motif."""
     if (k is None) == (ratio is None):
         raise ValueError("give exactly one of k and ratio")
     a = ops.edge_tensor(att)
@@ -311,6 +313,9 @@ def explanation_subgraph(att, data, k: Optional[int] = None, ratio: Optional[flo
     mask = topk_edge_mask(a, data.edge_index, data.batch, k=k, ratio=ratio, num_graphs=getattr(data, "num_graphs", None), path=path)
     if complement:
         mask = ~mask
+    if connected:
+        from .explain import largest_component_mask
+        mask = largest_component_mask(data.edge_index, data.batch, mask, num_graphs=getattr(data, "num_graphs", None))
     sub = edge_subgraph(data, mask, drop_isolated=drop_isolated)
     sub.edge_att = gather_rows(a.detach(), sub.edge_id)
     return sub

@@ -30,6 +30,9 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
   * ``--graph [--ragged] --fidelity-curve 0.1,0.2,...`` -- each report line is followed by one line per sparsity level: the fidelity of
     the top-ratio explanation on the test split at every ratio (``dp_gsat_amd.ReplayedFidelityCurve``).  One captured graph ranks the
     edges once, stacks the batch, every explanation and every complement into ONE batch and runs the backbone once.
+    ``--connectivity`` adds four lines under the curve: per level the mean number of connected components of the kept edges per graph,
+    the share of kept edges and of touched nodes inside the largest component, and the fraction of graphs whose explanation is ONE
+    piece (``connectivity=True``: one more kernel per batch in the same captured graph, one more host read per epoch).
 
   * ``--node-attention`` -- the extractor scores nodes (``learn_edge_att=False``); the edge attention is the lifted product.  With it,
     ``--fidelity-curve ... --fidelity-unit node`` ranks the NODES: every level keeps (or removes) the top-ratio nodes of each graph and
@@ -106,6 +109,8 @@ def main():
                     help="with --graph: print the fidelity of the top-ratio explanation on the test split at every ratio (increasing, in (0, 1])")
     ap.add_argument("--fidelity-unit", default="edge", choices=["edge", "node"],
                     help="with --fidelity-curve: rank and remove edges, or the nodes of a --node-attention model")
+    ap.add_argument("--connectivity", action="store_true",
+                    help="with --fidelity-curve (edges): print how connected the kept edges are at every ratio")
     ap.add_argument("--pretrain", type=int, default=0, metavar="N",
                     help="with --graph: pre-train the backbone alone for N epochs (pretrain_clf) and start GSAT from it")
     ap.add_argument("--node-attention", action="store_true", help="learn node attention (learn_edge_att=False) instead of edge attention")
@@ -122,6 +127,8 @@ def main():
         ap.error("--fidelity replays a captured fidelity batch: it needs --graph")
     if args.fidelity_curve is not None and not args.graph:
         ap.error("--fidelity-curve replays a captured stacked batch: it needs --graph")
+    if args.connectivity and (args.fidelity_curve is None or args.fidelity_unit != "edge"):
+        ap.error("--connectivity scores the kept edges of --fidelity-curve: it needs it, with --fidelity-unit edge")
     if args.pretrain and not args.graph:
         ap.error("--pretrain replays the classifier step: it needs --graph")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
@@ -188,7 +195,7 @@ def main():
             replayed_fidelity = G.ReplayedFidelity(gsat, ds, slots, k=args.fidelity, capacity=capacity, ragged=True)
         if args.fidelity_curve is not None:
             replayed_curve = G.ReplayedFidelityCurve(gsat, ds, slots, ratios=args.fidelity_curve, capacity=capacity, ragged=True,
-                                                     unit=args.fidelity_unit)
+                                                     unit=args.fidelity_unit, connectivity=args.connectivity)
     elif args.graph and n_train >= args.batch_size:
         replayed = G.ReplayedStep(gsat, ds, args.batch_size)      # capacity: ds.capacity_for(batch_size), which no batch exceeds
     if args.graph and not args.ragged:
@@ -197,7 +204,7 @@ def main():
             replayed_fidelity = G.ReplayedFidelity(gsat, ds, min(args.batch_size, len(graphs)), k=args.fidelity)
         if args.fidelity_curve is not None:
             replayed_curve = G.ReplayedFidelityCurve(gsat, ds, min(args.batch_size, len(graphs)), ratios=args.fidelity_curve,
-                                                     unit=args.fidelity_unit)
+                                                     unit=args.fidelity_unit, connectivity=args.connectivity)
 
     def evaluate_replayed(ids, epoch):
         res = replayed_eval.run(ids, epoch)      # full batches: replays; the tail: eager (--ragged: a replay too); one scoring pass at the end
@@ -249,6 +256,9 @@ def main():
                     print(f"      fidelity@{ratio:g}  kept {res['kept_fraction'][s]:.3f}{nodes}  fidelity_plus {res['fidelity_plus'][s]:.4f}  "
                           f"fidelity_minus {res['fidelity_minus'][s]:.4f}  flip_plus {res['flip_plus'][s]:.3f}  "
                           f"flip_minus {res['flip_minus'][s]:.3f}", flush=True)
+                if args.connectivity:
+                    for key in ("components", "largest_edge_share", "largest_node_share", "connected_fraction"):
+                        print(f"      {key:<19}" + "".join(f"  {v:.3f}" for v in res[key]), flush=True)
             if args.train_scores:                                 # scored from what the replays of this epoch logged: no eager batch
                 res = replayed.epoch_scores()
                 print(f"      train  loss {res['loss']:.4f}  pred {res['pred']:.4f}  info {res['info']:.4f}  acc {res['clf_acc']:.3f}  "

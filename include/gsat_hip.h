@@ -1288,6 +1288,50 @@ int gsat_fidelity_stack_nodes(const int64_t* edge_index, int64_t E, int64_t N, c
                               const int64_t* segment_offsets, int64_t* out_edge_index, int64_t* out_edge_id, int64_t* out_node_id,
                               int64_t* out_batch, int32_t* valid_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Connectivity of explanations: the connected components of every graph's kept edges at every level of a fidelity curve.
+ * edge_index int64[2, E]; node_ptr / edge_ptr int32[G' + 1] and edge_order int32[E] the nodes and the edge slots grouped by graph (the
+ * batch index's, G' >= G); level uint8[E] what gsat_fidelity_levels writes with 1 <= levels <= 16: level s keeps the slots with
+ * level[e] <= s, a byte of `levels` or above is in no level.  G: the graphs to look at, the first ones -- for a padded batch num_graphs - 1,
+ * so that the padding graph is never touched.  valid int32[4] (nullable, a padded batch's word): only the graphs below
+ * clamp(valid[2], 0, G) are looked at, none when valid[3] is set; an edge slot at or beyond clamp(valid[1], 0, E) is never loaded (neither
+ * its endpoints nor its level byte) and is kept at no level.
+ * Connectivity ignores direction; a self-loop joins nothing (its node is touched and its slot counts where its node's component
+ * counts); duplicate and one-directional edges are fine.  The nodes touched at level s are the endpoints of its kept slots.
+ *   per_graph int32[G, levels, 5] (nullable)  per graph g and level s: components among the touched nodes, kept slots, the most kept
+ *                                     slots inside one component, touched nodes, the most nodes inside one component (two independent
+ *                                     maxima); (0, 0, 0, 0, 0) with nothing kept
+ *   acc int64[levels, 8] (nullable)   ADDED to, per looked-at graph that is not skipped: acc[s] += (1, components, kept, big_edges,
+ *                                     touched, big_nodes, components == 1, 0); acc[0][7] counts the skipped graphs
+ *   node_comp int32[N] (nullable)     of the LAST level: the smallest node id (batch-global) of the node's component, -1 for an
+ *                                     untouched node
+ *   edge_big uint8[E] (nullable)      of the LAST level: 1 iff the slot is kept and lies in its graph's component with the most kept
+ *                                     slots, ties going to the component with the smaller label; 0 for every other loaded slot
+ * Rows and slots of graphs that are not looked at are not written; neither are node_comp / edge_big of a skipped graph, nor edge_big of
+ * a slot at or beyond valid[1].
+ * max_seg_nodes: the caller's bound on the nodes of one graph.  -1 (unknown) or above gsat_level_components_lds_cap(): GSAT_ERR_ARG,
+ * never a truncation.  A graph is SKIPPED WHOLE -- its per_graph rows are -1 and it adds 1 to acc[0][7] only -- when it has more nodes
+ * than max_seg_nodes, when its node or slot range is not inside [0, N] / [0, E], when one of its slots names an edge outside [0, E), or
+ * when a loaded slot has an endpoint outside the graph's node range; the checks run before anything is indexed with its ids.
+ * ONE launch, caller-owned outputs, no workspace, nothing read back: capturable.  A wavefront takes a graph of at most
+ * gsat_level_components_wave_nodes() = 64 nodes in an LDS slice of its own (no workgroup barrier in that tier), the workgroup a larger
+ * one up to the cap of 4096 nodes: 13 bytes of labels, counters and marks per node plus four packed edge words per node, 116 KiB of the
+ * 160 KiB LDS at the cap (slots beyond the kept words are re-read from global memory).  Labels start as the node's own id and are
+ * carried from level to level (the kept sets are nested); per level, min-label hooking by LDS atomicMin along the NEW slots and pointer
+ * jumping, rounds bounded by the node count; the counts are taken from LDS counters indexed by root after each level converges.  The
+ * fixed point is unique, so the result is integer, exact and bitwise repeatable whatever the order of the atomics.
+ * E, N, G >= 2^31: GSAT_ERR_UNSUPPORTED.
+ * replaces: the attention's copy to the host and a networkx / scipy connected-components loop over graphs and levels.
+ */
+int64_t gsat_level_components_lds_cap(void);
+int64_t gsat_level_components_wave_nodes(void);
+int gsat_level_components(const int64_t* edge_index, int64_t E, int64_t N, const int32_t* node_ptr, const int32_t* edge_ptr,
+                          const int32_t* edge_order, int64_t G, const uint8_t* level, int64_t levels, int64_t max_seg_nodes,
+                          const int32_t* valid, int32_t* per_graph, int64_t* acc, int32_t* node_comp, uint8_t* edge_big, void* stream);
+
+/* acc int64[levels, 8] = 0, by a kernel (no memset node). */
+int gsat_level_components_reset(int64_t* acc, int64_t levels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
