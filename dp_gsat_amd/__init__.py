@@ -36,6 +36,8 @@ from .replay import ReplayedClfEval, ReplayedClfStep
 from .pretrain import pretrain_clf, update_best_clf
 from .explain import (LevelComponents, component_labels, components_lds_cap, explanation_connectivity, largest_component_mask, level_components,
                       level_components_reset)
+from .baselines import Explanation, GNNExplainer, MaskState, edge_saliency, normalise_per_graph
+from .replay import ReplayedGNNExplainer
 
 __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "get_preds", "GINConv", "GINEConv",
            "PNAConvSimple", "GIN", "PNA", "GSAT", "ExtractorMLP", "concrete_sample", "get_r", "gumbel_sigmoid",
@@ -52,4 +54,5 @@ __all__ = ["MLP", "BatchSequential", "Criterion", "InstanceNorm", "get_model", "
            "ReplayedDualFidelityCurve", "NodeRanking", "rank_nodes", "topk_node_mask", "node_levels", "node_precision_at_k",
            "explanation_node_subgraph", "explanation_stack_nodes", "explanation_node_fidelity_curve",
            "ClfLog", "ReplayedClfStep", "ReplayedClfEval", "pretrain_clf", "update_best_clf", "LevelComponents", "components_lds_cap",
-           "level_components", "level_components_reset", "largest_component_mask", "component_labels", "explanation_connectivity"]
+           "level_components", "level_components_reset", "largest_component_mask", "component_labels", "explanation_connectivity",
+           "GNNExplainer", "Explanation", "MaskState", "edge_saliency", "normalise_per_graph", "ReplayedGNNExplainer"]

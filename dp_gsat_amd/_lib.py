@@ -170,6 +170,10 @@ SIGNATURES = {
     "gsat_level_components_wave_nodes": (I64, []),
     "gsat_level_components": (INT, [P, I64, I64, P, P, P, I64, P, I64, I64, P, P, P, P, P, P]),
     "gsat_level_components_reset": (INT, [P, I64, P]),
+    "gsat_mask_init": (INT, [P, F32, P, P, P, I64, I64, I64, F64, F64, P, P, P, P, P, P, P]),
+    "gsat_mask_step": (INT, [P, P, P, P, P, P, I64, I64, P, P, F32, F64, F64, F32, F32, F32, P]),
+    "gsat_mask_objective": (INT, [P, P, P, I64, I64, P, P, P]),
+    "gsat_segment_minmax_norm": (INT, [P, P, P, I64, I64, F32, F32, P, P, P]),
 }
 
 

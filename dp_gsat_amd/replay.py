@@ -1452,3 +1452,143 @@ class ReplayedDualFidelityCurve(_Replayed):
         """True if a batch or a variant of its stack since the last call (or since capture) did not fit its capacity.  One host read;
         clears the flag."""
         return _take_overflow(self)
+
+
+# ---- a post-hoc baseline: the batched GNNExplainer ------------------------------------------------------------------------------------------
+class ReplayedGNNExplainer(_ReplayedClf):
+    """``ReplayedGNNExplainer(clf, criterion, dataset, batch_size, k, steps=100, lr=0.01, betas=(0.9, 0.999), eps=1e-8, size_coef=0.005,
+    ent_coef=1.0, symmetric=True, target="model", capacity=None, ragged=False, bins=64, max_graphs=None, max_edges=None, graphs=None)``: an
+    explanation epoch of :class:`~dp_gsat_amd.baselines.GNNExplainer` on the bare backbone ``clf`` over ``dataset`` (a PackedDataset
+    with ``edge_label_all``), scored like GSAT's attention.  It holds THREE captured hipGraphs (``graphs``):
+
+      begin   clear_cache, ``collate_padded``, the unmasked eval-mode forward, the targets, ``gsat_mask_init``
+      step    the masked forward, the criterion, the backward to the mask, ``gsat_mask_step``
+      end     one masked forward under ``no_grad`` for the objective of the final mask, then ``log.append`` (an
+              :class:`~dp_gsat_amd.eval_log.EpochLog`) of the symmetrised mask, the unmasked logits and the triple (objective, its
+              prediction term, its regulariser)
+
+    and ``step(ids)`` replays begin, ``steps`` times step, then end: the step counter of the mask's Adam lives on the device, so ONE
+    captured step serves every iteration.  The step and end graphs read the batch, its index and the mask state at the addresses the
+    begin graph writes them to.  ``run(ids)`` resets the log, replays every full batch (ragged: every row of ``batches``), runs a
+    fixed-count tail eagerly through the same three phases and returns ``log.compute()`` -- the keys of ``ReplayedEval.run``, with
+    ``loss`` / ``pred`` / ``info`` the means over the batches of the triple above.
+
+    The graphs read the parameters and running statistics where they live and write none of them; no noise is drawn and the device seed
+    stream is left alone, so an explanation epoch between training steps does not change the training run.  Parameters are frozen
+    (``requires_grad``) while the graphs are captured and while a tail runs, and every flag is put back.
+
+    After ``step`` / ``run``: ``batch``, ``edge_att`` [E_cap, 1], ``mask_logits`` [E_cap], ``clf_logits`` [B + 1, C] and ``losses`` [3] of
+    the last replayed batch, for ``explanation_fidelity_curve`` or ``explanation_connectivity``.  A replay rewrites ``batch`` in place,
+    which the index cache cannot see: call ``clear_cache()`` before handing a replayed batch to an eager function.
+
+    Refused with ValueError before anything is captured: what ``ReplayedClfEval`` and ``GNNExplainer`` refuse, and a dataset without
+    ``edge_label_all``."""
+
+    _PHASES = ("begin", "step", "end")
+
+    def __init__(self, clf, criterion, dataset, batch_size: int, k: int, steps: int = 100, lr: float = 0.01, betas=(0.9, 0.999),
+                 eps: float = 1e-8, size_coef: float = 0.005, ent_coef: float = 1.0, symmetric: bool = True, target: str = "model",
+                 capacity: Optional[tuple] = None, ragged: bool = False, bins: int = 64, max_graphs: Optional[int] = None,
+                 max_edges: Optional[int] = None, graphs: Optional[tuple] = None):
+        from .baselines import GNNExplainer, MaskState
+        _clf_refusals("ReplayedGNNExplainer", clf, criterion, dataset)
+        self.explainer = GNNExplainer(clf, criterion, steps, lr, betas, eps, size_coef, ent_coef, symmetric, target)
+        if getattr(dataset, "edge_label_all", None) is None:
+            raise ValueError("ReplayedGNNExplainer needs a dataset with edge labels (edge_label_all)")
+        _check_log_sizes(k, bins)
+        self.model, self.criterion, self.dataset, self.steps = clf, criterion, dataset, self.explainer.steps
+        if graphs is not None and len(graphs) != 3:
+            raise ValueError("graphs is the triple (begin, step, end) of torch.cuda.CUDAGraph objects")
+        self._setup(clf, (dataset,), batch_size, capacity, None if graphs is None else graphs[0], ragged)
+        later = graphs[1:] if graphs is not None else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
+        self.graphs = self._graphs = dict(zip(self._PHASES, (self.graph,) + tuple(later)))
+        self.mask = MaskState(self.capacity[1], dataset.x_all.device)
+        self._ctx = self.log = self.batch = self.edge_att = self.mask_logits = self.clf_logits = self.losses = None
+        sizes = (int(k), int(bins), max_graphs, max_edges)
+        _capture_evaluator(self, lambda: self._make_log(sizes))
+
+    def _make_log(self, sizes):
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        with torch.no_grad():
+            logits = _clf_forward(self.model, self.criterion, b)[0]
+        self.log, = _new_logs(self, 1, logits, *sizes)
+
+    # -- the three bodies ------------------------------------------------------------------------------------------------------------
+    def _begin(self):
+        clear_cache()
+        b = self.dataset.collate_padded(self.graph_ids, self.capacity, ragged=self.ragged)
+        self._ctx = self.explainer.begin(b, self.mask)
+
+    def _step(self):
+        self.explainer.step(self._ctx, self.mask)
+
+    def _finish(self, ctx, mask):
+        """Objective of the final mask, the scored mask, the append; returns what a batch publishes."""
+        ex = self.explainer
+        with torch.no_grad():
+            pred, size, ent = ex.objective(ctx, mask).unbind(0)
+            reg = ex.size_coef * size + ex.ent_coef * ent
+            losses = torch.stack([pred + reg, pred, reg])
+            att = ex.edge_att(ctx, mask)
+            self.log.append(att, ctx["data"], ctx["logits"], losses)
+        return dict(batch=ctx["data"], edge_att=att, mask_logits=mask.m, clf_logits=ctx["logits"], losses=losses)
+
+    def _end(self):
+        self._publish(False, **self._finish(self._ctx, self.mask))
+
+    def run_once(self):
+        """begin, ``steps`` times step, end, eagerly on the current stream."""
+        self._begin()
+        for _ in range(self.steps):
+            self._step()
+        self._end()
+
+    def _warm_up_and_capture(self, setup=None, before_capture=None):
+        """``_Replayed``'s protocol for a chain of bodies: three eager runs of begin, step, end on a side stream, the one host read that
+        tells whether the warm-up batch fit, then one capture per phase, in order -- each phase is captured on what the capture of the
+        one before it left behind."""
+        from .baselines import _frozen
+        bodies = dict(begin=self._begin, step=self._step, end=self._end)
+        with _frozen(self.model):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                if setup is not None:
+                    setup()
+                for _ in range(3):
+                    for name in self._PHASES:
+                        bodies[name]()
+            torch.cuda.current_stream().wait_stream(side)
+            if int(self.batch.valid[3]) != 0:
+                raise ValueError(f"{type(self).__name__}: graphs 0..{self.batch_size - 1} do not fit the capacity {self.capacity}")
+            if before_capture is not None:
+                before_capture()
+            for name in self._PHASES:
+                with torch.cuda.graph(self._graphs[name]):
+                    bodies[name]()
+
+    def step(self, graph_ids, epoch: int = 0) -> None:
+        """Explain one batch: the ids are copied in, then begin, ``steps`` times step and end are replayed.  Nothing is read back."""
+        self._load_ids(graph_ids)
+        self._graphs["begin"].replay()
+        step = self._graphs["step"]
+        for _ in range(self.steps):
+            step.replay()
+        self._graphs["end"].replay()
+
+    def _forward(self, b, epoch=0):
+        """The eager tail: the same three phases on the collated batch ``b`` with a mask state of its size."""
+        from .baselines import MaskState, _frozen
+        mask = MaskState(int(b.edge_index.shape[1]), b.edge_index.device)
+        with _frozen(self.model):
+            ctx = self.explainer.begin(b, mask)
+            for _ in range(self.steps):
+                self.explainer.step(ctx, mask)
+            return self._finish(ctx, mask)
+
+    def run(self, graph_ids, epoch: int = 0) -> dict:
+        """One explanation epoch over ``graph_ids`` (any number, in visiting order): the log is reset, every full batch is replayed
+        (ragged: every row of ``batches``), a tail of fewer than ``batch_size`` graphs runs eagerly, and ``log.compute()`` -- two host
+        reads -- gives the scores.  The eager tail is logged but NOT published: afterwards ``batch``, ``edge_att`` and ``mask_logits`` are
+        those of the last REPLAYED batch, which is not the last batch of the epoch when there was a tail."""
+        return _run_epoch(self, graph_ids, 0)

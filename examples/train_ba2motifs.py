@@ -48,6 +48,7 @@ learned edge attention against the motif edges, scored on the device by dp_gsat_
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --train-scores
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --pretrain 10
+  python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --pretrain 10 --baseline gnnexplainer,saliency
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity 5
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --fidelity-curve 0.2,0.5,0.8
   python examples/train_ba2motifs.py --graphs 1000 --epochs 20 --graph --ragged --node-attention --fidelity-curve 0.2,0.5,0.8 --fidelity-unit node
@@ -114,6 +115,8 @@ def main():
     ap.add_argument("--pretrain", type=int, default=0, metavar="N",
                     help="with --graph: pre-train the backbone alone for N epochs (pretrain_clf) and start GSAT from it")
     ap.add_argument("--node-attention", action="store_true", help="learn node attention (learn_edge_att=False) instead of edge attention")
+    ap.add_argument("--baseline", type=lambda s: [v.strip() for v in s.split(",") if v.strip()], default=None, metavar="gnnexplainer,saliency",
+                    help="with --pretrain: after training, score post-hoc explanations of the pre-trained (ERM) backbone next to GSAT's attention")
     args = ap.parse_args()
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -131,6 +134,11 @@ def main():
         ap.error("--connectivity scores the kept edges of --fidelity-curve: it needs it, with --fidelity-unit edge")
     if args.pretrain and not args.graph:
         ap.error("--pretrain replays the classifier step: it needs --graph")
+    if args.baseline is not None:
+        if not args.pretrain:
+            ap.error("--baseline explains the ERM backbone that --pretrain trains: it needs --pretrain N")
+        if not args.baseline or any(b not in ("gnnexplainer", "saliency") for b in args.baseline):
+            ap.error("--baseline takes a comma-separated list of gnnexplainer and saliency")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     if world > 1:
@@ -152,6 +160,7 @@ def main():
                aggregators=["mean", "min", "max", "std", "sum"], scalers=False, deg=deg)
     clf = G.get_model(10, 0, 2, False, cfg, dev)
     ext = G.ExtractorMLP(args.hidden, not args.node_attention).to(dev)
+    erm_clf = None
     if args.pretrain > 0:
         # from_scratch: false -- ERM on the backbone alone, then the GSAT optimizer below over extractor + backbone (run_gsat.py:1005-1007)
         n_valid = max(1, (len(graphs) - n_train) // 2)
@@ -164,6 +173,9 @@ def main():
                   f"valid acc {r['valid']:.3f}  test acc {r['test']:.3f}", flush=True)
         print(f"pretrain best epoch {best['metric/best_clf_epoch'] + 1}  valid acc {best['metric/best_clf_valid']:.3f}  "
               f"test acc {best['metric/best_clf_test']:.3f}", flush=True)
+        if args.baseline is not None:
+            import copy
+            erm_clf = copy.deepcopy(clf)                          # GSAT trains clf on from here; the baselines explain the ERM backbone
     params = list(clf.parameters()) + list(ext.parameters())
     opt = torch.optim.Adam(params, lr=1e-3, weight_decay=3e-6, **(dict(capturable=True, fused=True) if args.graph else {}))
     gsat = G.GSAT(clf, ext, G.Criterion(2, False), opt, learn_edge_att=not args.node_attention)
@@ -263,6 +275,27 @@ def main():
                 res = replayed.epoch_scores()
                 print(f"      train  loss {res['loss']:.4f}  pred {res['pred']:.4f}  info {res['info']:.4f}  acc {res['clf_acc']:.3f}  "
                       f"clf ROC-AUC {res['clf_roc']:.3f}  attention ROC-AUC {res['att_auroc']:.3f}  prec@5 {res['precision@5']:.3f}", flush=True)
+    if rank == 0 and erm_clf is not None:
+        # GSAT's claim against post-hoc explainers, on the same test split and with the same two scores
+        test_ids = np.arange(n_train, len(graphs))
+        acc, auc, prec = evaluate_replayed(test_ids, args.epochs - 1) if replayed_eval is not None else evaluate(test_ids)
+        print(f"explanations on the test split ({len(test_ids)} graphs)", flush=True)
+        print(f"      {'GSAT attention':<26}  attention ROC-AUC {auc:.3f}  prec@5 {prec:.3f}  (test acc {acc:.3f})", flush=True)
+        for name in args.baseline:
+            if name == "gnnexplainer":                            # every batch three captured graphs: begin, 100 x step, end
+                slots = min(args.batch_size, len(graphs))
+                kw = dict(capacity=capacity, ragged=True) if args.ragged else {}
+                res = G.ReplayedGNNExplainer(erm_clf, G.Criterion(2, False), ds, slots, 5, **kw).run(test_ids)
+                auc, prec, acc = res["att_auroc"], res["precision@5"], res["clf_acc"]
+            else:                                                 # one forward and one backward of the whole split
+                b = ds.collate(torch.as_tensor(test_ids, device=dev))
+                sal = G.edge_saliency(erm_clf, b)
+                auc, prec = torch.stack([G.attention_auroc(sal, b.edge_label),
+                                         G.precision_at_k(sal, b.edge_label, 5, b.batch, b.edge_index, b.num_graphs).double().mean()]).tolist()
+                erm_clf.eval()
+                with torch.no_grad():
+                    acc = float(((erm_clf(b.x, b.edge_index, b.batch, edge_attr=b.edge_attr) > 0).float() == b.y).float().mean())
+            print(f"      {name + ' on the ERM backbone':<26}  attention ROC-AUC {auc:.3f}  prec@5 {prec:.3f}  (test acc {acc:.3f})", flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -1332,6 +1332,56 @@ int gsat_level_components(const int64_t* edge_index, int64_t E, int64_t N, const
 /* acc int64[levels, 8] = 0, by a kernel (no memset node). */
 int gsat_level_components_reset(int64_t* acc, int64_t levels, void* stream);
 
+/*
+ * Post-hoc edge-mask explainer (PyG's GNNExplainer with edge_reduction = 'sum' for the size term and a mean for the entropy) around the
+ * mask-weighted message passing.  One mask logit m per edge slot, a = sigmoid(m) is what the backbone takes as edge_atten.  The
+ * objective of a batch is the sum over its real graphs of a per-graph objective, so a graph's mask does not depend on its batch:
+ *   L = sum_g crit_g(z_g, t_g) + sum_e [ size_coef a_e + ent_coef H(a_e) / E_g(e) ],   H(a) = -a ln(a + 1e-15) - (1 - a) ln(1 - a + 1e-15)
+ * with E_g(e) the edge count of the graph of e's source node.
+ *
+ * gsat_mask_init -- ONE launch over all E slots (the capacity of a padded batch), so that a captured body needs no memset:
+ *   m <- init[e] (init float32[E], nullable) or init_value;  mu = nu = 0;  a = sigmoid(m);
+ *   inv_eg[e] = 1 / E_g(e) from src32 int32[E], node_seg32 int32[N] (graph of every node) and edge_ptr int32[G + 1] (edge slots grouped
+ *   by graph); 1 for a slot whose ids are out of range;
+ *   state float32[4] = (steps taken t = 0, 1 / (1 - b1^(t + 1)), 1 / sqrt(1 - b2^(t + 1)), 0) -- the bias corrections of the NEXT step,
+ *   evaluated in fp64 from the fp64 betas as torch's Adam evaluates them on the host (1 - b2^t of a b2 rounded to fp32 would be off
+ *   by 1e-5 of itself in the first steps; the moments use 1 - beta rounded once from fp64).  E = 0 writes the state alone.
+ *
+ * gsat_mask_step -- one elementwise launch, then one single-thread launch that advances `state` (the elementwise launch only READS
+ * it, so no workgroup can see a counter another one has moved: a captured step can be replayed T times).  valid int32[4] (nullable): a
+ * padded batch's word (N_real, E_real, graphs, overflow); m_valid = clamp(valid[1], 0, E), b = clamp(valid[2], 0, G); without it m_valid
+ * = E and b = G.  g_a float32[E] is the gradient of the project's MEAN criterion over the b graphs with respect to a; the factor b, read
+ * on the device, turns it into the gradient of the per-graph sum.  For e < m_valid:
+ *   G_e = a (1 - a) (b g_a[e] + size_coef + ent_coef dH/da inv_eg[e])
+ *   dH/da = -ln(a + 1e-15) - a / (a + 1e-15) + ln(1 - a + 1e-15) + (1 - a) / (1 - a + 1e-15)
+ *   mu = b1 mu + (1 - b1) G;  nu = b2 nu + (1 - b2) G^2;  m -= lr state[1] mu / (sqrt(nu) state[2] + eps);  a = sigmoid(m)
+ * which is torch.optim.Adam without weight decay and amsgrad.  Entries at or beyond m_valid are neither loaded nor written; a batch
+ * whose valid[3] is set changes nothing, the state included; E = 0 is a no-op.  A saturated logit (a = 0 or 1 in fp32) has G = 0 and
+ * every term stays finite.  Four entries per thread, 16-byte accesses when the six arrays are 16-byte aligned.  No atomics: bitwise
+ * repeatable.  lr > 0, betas in [0, 1), eps, size_coef, ent_coef >= 0 (GSAT_ERR_ARG otherwise).
+ * replaces: sigmoid, the two regularisers and their autograd, the chain through the sigmoid and the optimiser's launches per step.
+ *
+ * gsat_mask_objective -- out float32[G, 2] = per graph (sum of a, mean of H(a)) over the graph's slots edge_order[edge_ptr[g] ..
+ * edge_ptr[g + 1]); one wavefront per graph, lanes stride the slots, fixed-order sums; any graph size.  Graphs at or beyond b, and
+ * every graph of an overflowing batch, get (0, 0); slots at or beyond m_valid are not loaded.
+ *
+ * gsat_segment_minmax_norm -- out[e] = (att[e]^power - min_g) / (max_g - min_g + eps) with the minimum and maximum of att^power over
+ * the slots of e's graph, through edge_order (not assumed to be the identity).  power = 10, eps = 1e-6 is the rule of the
+ * reference's visualize_a_graph(norm=True); power = 1 is plain min-max (no pow is evaluated).  A graph with one edge and a constant
+ * graph give 0; slots of graphs at or beyond b or at or beyond m_valid get 0 without a load.  One wavefront per graph, two passes.
+ * Every extent < 2^31 (GSAT_ERR_UNSUPPORTED otherwise).
+ */
+int gsat_mask_init(const float* init, float init_value, const int32_t* src32, const int32_t* node_seg32, const int32_t* edge_ptr, int64_t N,
+                   int64_t G, int64_t E, double b1, double b2, float* m, float* mu, float* nu, float* a, float* inv_eg, float* state,
+                   void* stream);
+int gsat_mask_step(float* m, float* mu, float* nu, float* a, const float* g_a, const float* inv_eg, int64_t E, int64_t G,
+                   const int32_t* valid, float* state, float lr, double b1, double b2, float eps, float size_coef, float ent_coef,
+                   void* stream);
+int gsat_mask_objective(const float* a, const int32_t* edge_ptr, const int32_t* edge_order, int64_t E, int64_t G, const int32_t* valid,
+                        float* out, void* stream);
+int gsat_segment_minmax_norm(const float* att, const int32_t* edge_ptr, const int32_t* edge_order, int64_t E, int64_t G, float power,
+                             float eps, const int32_t* valid, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
